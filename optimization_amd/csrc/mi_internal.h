@@ -81,6 +81,10 @@ struct CgState {
   unsigned long long launches;     // B-step launches that found the solve still running (progress word)
   int mode;                        // CgMode
   int exit_reason;
+  // deferred-s form (stpcg.hip k_cg_pupdate_ds): the alpha of the even iteration whose s += alpha p is still pending.
+  // Written and read by the direction kernels ONLY, in the copy they write (it is not one of CG_FIELDS: k_cg_update
+  // neither loads nor stores it)
+  double alpha_prev;
 };
 static_assert(sizeof(CgState) <= 128, "the CG state is meant to fit one 128-byte line");
 // Per-solve constants known on the host travel as kernel arguments (SGPRs), not through the state.
@@ -134,6 +138,9 @@ struct Config {
                                     // rank forms halo(p') = -halo(r') + beta halo(p) itself: 2 collectives per iteration
                                     // instead of 3 on the RCCL layer (`--comm rccl2`)
   bool early_s = false;             // EARLY_S: the direction kernel of the single-context recurrence solve applies s += alpha p AHEAD of its reduction (k_cg_pupdate_early; opt-in experiment, same bits, same time)
+  bool defer_s = true;              // DEFER_S: the single-context solve with the flat direction kernel adds the step up every SECOND
+                                    // iteration, s = (s + alpha_k p_k) + alpha_k+1 p_k+1, from two alternating direction buffers
+                                    // (k_cg_pupdate_ds; same bits, 4.5 N instead of 5 N doubles per iteration); 0: every iteration
   bool so3_no_rquat = false;        // SO3_NO_RQUAT: the SO(3)^N model assembly gathers the neighbours' rotations as 72-byte matrices
                                     // (r05 form) instead of 32-byte quaternions written by the retraction (r06; creation-time)
   bool so3_no_quat = false;         // SO3_NO_QUAT: the measurements of mi_so3n stay 3 x 3 matrices (r04 form; creation-time)

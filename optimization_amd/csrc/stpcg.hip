@@ -378,6 +378,7 @@ struct DirGramLds<0> {
 static_assert(kWaves + 1 >= kIpcVals, "LDS of the folded exchange");
 
 #define CG_KERNEL_ATTR
+#define CG_UPDATE_SIGMA 1
 #define CG_UPDATE_NAME k_cg_update
 #define CG_PUPDATE_NAME k_cg_pupdate
 #include "stpcg_kernels.inc"
@@ -397,6 +398,27 @@ static_assert(kWaves + 1 >= kIpcVals, "LDS of the folded exchange");
 #undef CG_KERNEL_ATTR
 #undef CG_UPDATE_NAME
 #undef CG_PUPDATE_NAME
+#undef CG_UPDATE_SIGMA
+// k_cg_update WITHOUT the boundary step's s += sigma p: the A-step of an odd iteration of the deferred-s form (below,
+// k_cg_pupdate_ds), where the direction kernel behind it applies that step after the pending term.  A third and fourth
+// inclusion, not a template parameter or a flag: the kernels above keep their code, their registers and their names.
+// (the direction kernel of these inclusions is never instantiated)
+#define CG_UPDATE_SIGMA 0
+#define CG_KERNEL_ATTR
+#define CG_UPDATE_NAME k_cg_update_ns
+#define CG_PUPDATE_NAME k_cg_pupdate_ns_unused
+#include "stpcg_kernels.inc"
+#undef CG_KERNEL_ATTR
+#undef CG_UPDATE_NAME
+#undef CG_PUPDATE_NAME
+#define CG_KERNEL_ATTR __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8, 8)))
+#define CG_UPDATE_NAME k_cg_update_ns_s80
+#define CG_PUPDATE_NAME k_cg_pupdate_ns_s80_unused
+#include "stpcg_kernels.inc"
+#undef CG_KERNEL_ATTR
+#undef CG_UPDATE_NAME
+#undef CG_PUPDATE_NAME
+#undef CG_UPDATE_SIGMA
 
 // EARLY S (late r06): the direction kernel of the single-context solve without a preconditioner (v = r, plain vectors,
 // G(p) by recurrence).  alpha is the A-step's -- it is in the state this kernel STARTS from -- so s += alpha p (:374)
@@ -537,6 +559,137 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
       s[n - 1] = s[n - 1] + alpha * p[n - 1];
       if (dir) p[n - 1] = -v[n - 1] + beta * p[n - 1];
     }
+  }
+}
+
+
+// DEFERRED S: the direction kernel of the single-context solve in its flat form, with the step added up every SECOND
+// iteration.  Nothing inside a solve reads s except the next s += alpha p (the boundary test runs on the scalar M-norm
+// recurrences), so with the direction in two alternating buffers the kernel of an even iteration k leaves s alone --
+//   <false>  reads v, pc = p_k;  writes px = p_k+1 = -v + beta p_k                                            [3 N]
+// and the kernel of the odd iteration behind it adds both terms, in today's order and with today's roundings --
+//   <true>   reads v, pc = p_k, px = p_k-1, s;  writes s = (s + alpha_k-1 p_k-1) + alpha_k p_k,
+//            and px = p_k+1 = -v + beta p_k over p_k-1 (same thread, same element, read before written)       [6 N]
+// 4.5 N doubles per iteration on average instead of k_cg_pupdate's 5 N.  A term is pending only while an odd iteration
+// runs, and every way out of the solve adds it first:
+//   * the B-step ends the solve at an even k: <false> applies s += alpha p itself (:374 is applied whatever :408-417
+//     decide) and writes no direction; at an odd k <true> adds its two terms as always;
+//   * boundary / negative curvature (:347-361) at an odd k: k_cg_update_ns (no s += sigma p) runs in k_cg_update's
+//     place and <true> adds (s + alpha_k-1 p_k-1) + sigma p_k; at an even k k_cg_update applies it as ever;
+//   * p in ker H (:305-337) at an odd k: the same with the sigma of this kernel's own B-step; at an even k as k_cg_pupdate.
+// The host picks the form from its loop index, which equals the state's k for as long as the solve runs; the LAST
+// enqueued iteration, when it is an even one, is k_cg_pupdate itself (nothing could be deferred to).  alpha_k-1
+// travels in CgState::alpha_prev of the copy the direction kernels write (k_cg_update overwrites alpha and does not carry
+// alpha_prev).  Prologue, walk and expressions are k_cg_pupdate<false, 0>'s: same translation unit, same contraction,
+// same bits (tests/test_gpu_deferred_s.py).
+template <bool FLUSH>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cg_pupdate_ds(
+    size_t n, CgConst cc, const CgState *__restrict__ st_in, CgState *__restrict__ st_out,
+    const double *__restrict__ partials_b, int nparts_b, const double *__restrict__ v, const double *__restrict__ pc,
+    double *__restrict__ px, double *__restrict__ s, HostStatus *hs, double *__restrict__ trace, size_t trace_cap,
+    DirGramArgs dg) {
+  __shared__ double lds[kWaves + 1];
+  CgState cs = load_state(st_in);
+  const bool leader = blockIdx.x == 0 && threadIdx.x == 0;
+  if (cs.mode == CG_DONE) {
+    if (leader) store_state(st_out, cs);
+    return;
+  }
+  const int mode_in = cs.mode;
+  const size_t n2 = n >> 1, stride = (size_t)gridDim.x * kBlock;
+  const size_t i0 = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  // (the walk of k_cg_pupdate, stpcg_kernels.inc: whole grid-stride steps, then the ragged rest in equal shares)
+  const size_t tail0 = cc.rag0, per = cc.rag_per;
+  const size_t irem = (threadIdx.x < per) ? tail0 + (size_t)blockIdx.x * per + threadIdx.x : n2;
+  auto next_of = [&](size_t i_) -> size_t {
+    const size_t j_ = i_ + stride;
+    return j_ < tail0 ? j_ : ((i_ < tail0 && irem < n2) ? irem : n2);
+  };
+  const size_t ifirst = i0 < tail0 ? i0 : (irem < n2 ? irem : n2);
+  double2 vv0 = make_double2(0, 0), pv0 = vv0, ov0 = vv0, sv0 = vv0;
+  auto prefetch_now = [&] {
+    if (ifirst < n2) {
+      vv0 = reinterpret_cast<const double2 *>(v)[ifirst];
+      pv0 = reinterpret_cast<const double2 *>(pc)[ifirst];
+      if (FLUSH) {
+        ov0 = reinterpret_cast<double2 *>(px)[ifirst];
+        sv0 = reinterpret_cast<double2 *>(s)[ifirst];
+      }
+    }
+  };
+  double red[1] = {0};
+  if (mode_in != CG_APPLY_SIGMA) reduce_rows<1>(partials_b, nparts_b, red, lds, prefetch_now);
+  else prefetch_now();
+  step_b(cs, cc, red[0]);
+  cs.launches = cs.launches + 1;
+  const bool dir = mode_in == CG_RUN && cs.mode == CG_RUN;
+  if (leader) {
+    store_state(st_out, cs);
+    if (!FLUSH && dir) st_out->alpha_prev = cs.alpha;  // s += alpha p of this iteration is pending
+    if (mode_in == CG_RUN && trace && cs.k - 1 < trace_cap) {
+      const size_t k = (size_t)(cs.k - 1);
+      trace[k] = cs.alpha;
+      trace[trace_cap + k] = cs.beta;
+      trace[2 * trace_cap + k] = cs.kappa;
+      trace[3 * trace_cap + k] = cs.rv;
+    }
+    publish(hs, cs.launches, cs.mode == CG_DONE);
+    if (dg.gdir && dir) {  // G(p) = -G(r) + beta G(p)  (:420)
+      for (int i = 0; i < dg.ns; ++i) dg.gdir[SLOT_GDIR_P + i] = -dg.gdir[i] + cs.beta * dg.gdir[SLOT_GDIR_P + i];
+    }
+  }
+  const double beta = cs.beta;
+  if (FLUSH) {
+    // the pending term, then this iteration's: alpha p (:374), or the sigma p of a boundary (:360) or kernel (:336) exit
+    const double alpha_old = st_out->alpha_prev, alpha = mode_in == CG_RUN ? cs.alpha : cs.sigma;
+    double2 vv = vv0, pv = pv0, ov = ov0, sv = sv0;
+    for (size_t i = ifirst; i < n2;) {
+      const size_t inext = next_of(i);
+      double2 vn = vv, pn = pv, on = ov, sn = sv;
+      if (inext < n2) {
+        vn = reinterpret_cast<const double2 *>(v)[inext];
+        pn = reinterpret_cast<const double2 *>(pc)[inext];
+        on = reinterpret_cast<double2 *>(px)[inext];
+        sn = reinterpret_cast<double2 *>(s)[inext];
+      }
+      sv.x = sv.x + alpha_old * ov.x; sv.y = sv.y + alpha_old * ov.y;
+      sv.x = sv.x + alpha * pv.x; sv.y = sv.y + alpha * pv.y;
+      reinterpret_cast<double2 *>(s)[i] = sv;
+      if (dir) {
+        pv.x = -vv.x + beta * pv.x; pv.y = -vv.y + beta * pv.y;
+        reinterpret_cast<double2 *>(px)[i] = pv;
+      }
+      i = inext; vv = vn; pv = pn; ov = on; sv = sn;
+    }
+    if ((n & 1) && leader) {
+      s[n - 1] = s[n - 1] + alpha_old * px[n - 1];
+      s[n - 1] = s[n - 1] + alpha * pc[n - 1];
+      if (dir) px[n - 1] = -v[n - 1] + beta * pc[n - 1];
+    }
+  } else if (dir) {
+    double2 vv = vv0, pv = pv0;
+    for (size_t i = ifirst; i < n2;) {
+      const size_t inext = next_of(i);
+      double2 vn = vv, pn = pv;
+      if (inext < n2) {
+        vn = reinterpret_cast<const double2 *>(v)[inext];
+        pn = reinterpret_cast<const double2 *>(pc)[inext];
+      }
+      pv.x = -vv.x + beta * pv.x; pv.y = -vv.y + beta * pv.y;
+      reinterpret_cast<double2 *>(px)[i] = pv;
+      i = inext; vv = vn; pv = pn;
+    }
+    if ((n & 1) && leader) px[n - 1] = -v[n - 1] + beta * pc[n - 1];
+  } else if (mode_in != CG_APPLY_SIGMA) {
+    // the solve ends at this even iteration and nothing is pending: alpha p (:374), or sigma p of the kernel exit (:336)
+    const double alpha = mode_in == CG_RUN ? cs.alpha : cs.sigma;
+    for (size_t i = i0; i < n2; i += stride) {
+      const double2 pv = reinterpret_cast<const double2 *>(pc)[i];
+      double2 sv = reinterpret_cast<double2 *>(s)[i];
+      sv.x = sv.x + alpha * pv.x; sv.y = sv.y + alpha * pv.y;
+      reinterpret_cast<double2 *>(s)[i] = sv;
+    }
+    if ((n & 1) && leader) s[n - 1] = s[n - 1] + alpha * pc[n - 1];
   }
 }
 
@@ -961,7 +1114,7 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
   // the failure word is per solve: a NaN residual in one solve must not condemn the object for the next
   if (P && P->fail_word) MI_HIP(hipMemsetAsync(P->fail_word, 0, sizeof(double), ctx->stream));
 
-  mi_vec *r = nullptr, *v = nullptr, *p = nullptr, *Hp = nullptr;
+  mi_vec *r = nullptr, *v = nullptr, *p = nullptr, *p2 = nullptr, *Hp = nullptr;
   MI_TRY(mi_vec_create(ctx, n, &r));
   MI_TRY(mi_vec_create(ctx, n, &p));
   MI_TRY(mi_vec_create(ctx, n, &Hp));
@@ -1032,9 +1185,25 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
   // opt-in experiment: the two-kernel step (k_cg_step2; one rank, Stiefel(n,3) in the window form)
   const bool twok = ctx->cfg.two_kernel_step && recur && dgp->twok && dgp->p == 3 && !sharded && !rows && !lockstep &&
                     init_fused && gdir_in_scalar_init;
+  // (the early-s form: single context, v = r or any plain vector, at most three elements per thread, <= 512 rows)
+  const bool early = !sharded && !rows && sp == 0 && ctx->cfg.early_s && grid <= 512 &&
+                     cc.rag0 <= 2ull * (size_t)grid * kBlock && (n >> 1) < ((size_t)1 << 31);
+  // deferred-s form (k_cg_pupdate_ds): single context, flat direction kernel; the direction lives in two buffers that
+  // swap every iteration -- `p` is the current one wherever this function names it
+  const bool defer = !sharded && !rows && !lockstep && !twok && sp == 0 && !early && ctx->cfg.defer_s;
   CgState *st_final = st0;
   double *tr = tcap ? ctx->trace_dev : nullptr;
   int ret = MI_OK;
+  if (defer) {
+    const int st_p2 = mi_vec_create(ctx, n, &p2);
+    if (st_p2 != MI_OK) {
+      mi_vec_destroy(r);
+      mi_vec_destroy(p);
+      mi_vec_destroy(Hp);
+      if (v) mi_vec_destroy(v);
+      return st_p2;
+    }
+  }
   ctx->cg_live = st0;
 
 #define CG_CHECK(expr)   \
@@ -1052,12 +1221,12 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
     case PRE_BLOCK3: hipLaunchKernelGGL((KERNEL<PRE_BLOCK3>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__); break; \
     default: hipLaunchKernelGGL((KERNEL<PRE_EXTERNAL>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__); break;       \
   }
-#define LAUNCH_UPDATE(FS)                                                                              \
+#define LAUNCH_UPDATE(KN, FS)                                                                          \
   switch (pre) {                                                                                       \
-    case PRE_NONE: hipLaunchKernelGGL((k_cg_update<PRE_NONE, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;     \
-    case PRE_DIAG: hipLaunchKernelGGL((k_cg_update<PRE_DIAG, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;     \
-    case PRE_BLOCK3: hipLaunchKernelGGL((k_cg_update<PRE_BLOCK3, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-    default: hipLaunchKernelGGL((k_cg_update<PRE_EXTERNAL, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;       \
+    case PRE_NONE: hipLaunchKernelGGL((KN<PRE_NONE, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;     \
+    case PRE_DIAG: hipLaunchKernelGGL((KN<PRE_DIAG, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;     \
+    case PRE_BLOCK3: hipLaunchKernelGGL((KN<PRE_BLOCK3, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
+    default: hipLaunchKernelGGL((KN<PRE_EXTERNAL, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;       \
   }
 
   // --- initialisation -----------------------------------------------------------------------
@@ -1205,6 +1374,8 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
         CG_CHECK(launch_dot3_partials(ctx, n, p->d, Hp->d, &nparts));
       }
       ++hvp;
+      // (deferred-s form, odd k: a term of s is pending, and a boundary step is the direction kernel's to apply behind it)
+      const bool sigma_later = defer && (k & 1);
 #define UPD_ARGS                                                                                      \
   n, cc, (const CgState *)st0, st1, (const double *)ctx->partials, nparts,                              \
       (const double *)(recur ? slots_g : slots_a), (const double *)p->d, (const double *)Hp->d, pred,  \
@@ -1212,52 +1383,53 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
       if (recur) {
         // 3 dots + the Gram rows of Hp in one reduction (and one exchange across ranks)
         // KN: k_cg_update, or its 80-SGPR twin for the instantiations that need more (see above; 16 components always do)
-#define UPD_RECUR(KN, FS, FT, FV)                                                                                  \
+#define UPD_RECUR(KN, K16, FS, FT, FV)                                                                             \
   switch (kc) {                                                                                                    \
     case 4: hipLaunchKernelGGL((KN<PRE_NONE, FS, 4, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break;   \
     case 6: hipLaunchKernelGGL((KN<PRE_NONE, FS, 6, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break;   \
     case 9: hipLaunchKernelGGL((KN<PRE_NONE, FS, 9, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break;   \
-    default: hipLaunchKernelGGL((k_cg_update_s80<PRE_NONE, FS, 16, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break; \
+    default: hipLaunchKernelGGL((K16<PRE_NONE, FS, 16, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break; \
   }
   // p = 5 ... 8: 18, 24, 31, 39 components (3 + p (p + 1) / 2).  Never folded (the host keeps the separate exchange for
   // them), and launched from the uncapped kernel: 39 reduced values per thread do not fit the 64 vector registers the
   // two-workgroups-per-CU twins are held to
-#define UPD_WIDE(FS)                                                                                                        \
+#define UPD_WIDE(KN, FS)                                                                                                    \
   switch (kc) {                                                                                                             \
-    case 18: hipLaunchKernelGGL((k_cg_update<PRE_NONE, FS, 18, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-    case 24: hipLaunchKernelGGL((k_cg_update<PRE_NONE, FS, 24, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-    case 31: hipLaunchKernelGGL((k_cg_update<PRE_NONE, FS, 31, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-    default: hipLaunchKernelGGL((k_cg_update<PRE_NONE, FS, 39, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
+    case 18: hipLaunchKernelGGL((KN<PRE_NONE, FS, 18, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
+    case 24: hipLaunchKernelGGL((KN<PRE_NONE, FS, 24, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
+    case 31: hipLaunchKernelGGL((KN<PRE_NONE, FS, 31, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
+    default: hipLaunchKernelGGL((KN<PRE_NONE, FS, 39, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
   }
         if (kc > 16) {
           if (sharded) CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials, nparts, kc, slots_g));
           else if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials, kc));
           KScope ks(ctx, MI_K_CG_UPDATE);
-          if (sharded) { UPD_WIDE(true); } else { UPD_WIDE(false); }
+          if (sharded) { UPD_WIDE(k_cg_update, true); } else if (sigma_later) { UPD_WIDE(k_cg_update_ns, false); } else { UPD_WIDE(k_cg_update, false); }
         } else if (sharded && folded) {
           // the sum over the ranks completes in the kernel's own prologue (comm_ipc.h): no exchange kernel
           const FoldArgs fold_a = comm_fold_next(ctx);
           KScope ks(ctx, MI_K_CG_UPDATE);
-          UPD_RECUR(k_cg_update_s80, false, FoldArgs, fold_a);
+          UPD_RECUR(k_cg_update_s80, k_cg_update_s80, false, FoldArgs, fold_a);
         } else if (sharded) {
           CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials, nparts, kc, slots_g));
           KScope ks(ctx, MI_K_CG_UPDATE);
-          UPD_RECUR(k_cg_update_s80, true, NoFold, NoFold{});
+          UPD_RECUR(k_cg_update_s80, k_cg_update_s80, true, NoFold, NoFold{});
         } else {
           if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials, kc));
           KScope ks(ctx, MI_K_CG_UPDATE);
-          UPD_RECUR(k_cg_update, false, NoFold, NoFold{});
+          if (sigma_later) { UPD_RECUR(k_cg_update_ns, k_cg_update_ns_s80, false, NoFold, NoFold{}); }
+          else { UPD_RECUR(k_cg_update, k_cg_update_s80, false, NoFold, NoFold{}); }
         }
 #undef UPD_RECUR
 #undef UPD_WIDE
       } else if (sharded) {
         CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials, nparts, 3, slots_a));
         KScope ks(ctx, MI_K_CG_UPDATE);
-        LAUNCH_UPDATE(true);
+        LAUNCH_UPDATE(k_cg_update, true);
       } else {
         if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials, 3));
         KScope ks(ctx, MI_K_CG_UPDATE);
-        LAUNCH_UPDATE(false);
+        if (sigma_later) { LAUNCH_UPDATE(k_cg_update_ns, false); } else { LAUNCH_UPDATE(k_cg_update, false); }
       }
 #undef UPD_ARGS
       if (pre == PRE_EXTERNAL) {
@@ -1301,15 +1473,24 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
         if (rows && rprime) CG_CHECK(comm_rprime_exchange(ctx, dgp->halo_A, dgp->p, r->d, ctx->partials_b, 1));
         else if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials_b, 1));
         KScope ks(ctx, MI_K_CG_PUPDATE);
-        // (the early-s form: single context, v = r or any plain vector, at most three elements per thread, <= 512 rows)
-        const bool early = sp == 0 && !rows && ctx->cfg.early_s && grid <= 512 && cc.rag0 <= 2ull * (size_t)grid * kBlock &&
-                           (n >> 1) < ((size_t)1 << 31);
-        if (early)
+#define PUPD_DS(FLUSH)                                                                                                  \
+  hipLaunchKernelGGL(k_cg_pupdate_ds<FLUSH>, dim3(grid), dim3(kBlock), 0, st, n, cc, (const CgState *)st1, st0,          \
+                     (const double *)ctx->partials_b, grid, (const double *)vd, (const double *)p->d, p2->d, s_out->d, \
+                     ctx->status_dev, tr, tcap, dga)
+        if (early) {
           hipLaunchKernelGGL(k_cg_pupdate_early, dim3(grid), dim3(kBlock), 0, st, n, cc, (const CgState *)st1, st0,
                              (const double *)ctx->partials_b, grid, (const double *)vd, p->d, s_out->d, ctx->status_dev, tr,
                              tcap, dga);
-        else
+        } else if (defer && (k & 1)) {
+          PUPD_DS(true);
+          std::swap(p, p2);
+        } else if (defer && k + 1 < prm->max_iterations) {
+          PUPD_DS(false);
+          std::swap(p, p2);
+        } else {  // (deferred-s form: the last enqueued iteration is an even one)
           LAUNCH_PUPD(k_cg_pupdate, k_cg_pupdate_s80, false);
+        }
+#undef PUPD_DS
       }
       if (rprime && (sharded || rows)) {
         const double *hr = nullptr;
@@ -1404,6 +1585,7 @@ cleanup:
   if (ret != MI_OK) (void)hipStreamSynchronize(st);
   mi_vec_destroy(r);
   mi_vec_destroy(p);
+  mi_vec_destroy(p2);
   mi_vec_destroy(Hp);
   mi_vec_destroy(v);
   return ret;

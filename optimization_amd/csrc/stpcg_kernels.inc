@@ -1,6 +1,6 @@
-// stpcg_kernels.inc -- the two kernels of a fused STPCG iteration (stpcg.hip), included TWICE: as k_cg_update /
-// k_cg_pupdate, and as k_cg_update_s80 / k_cg_pupdate_s80 with the scalar-register budget capped at 80 (stpcg.hip says
-// why).  Textual inclusion, not a shared __device__ body: the first pair -- the single-GPU step -- must keep the exact
+// stpcg_kernels.inc -- the two kernels of a fused STPCG iteration (stpcg.hip), included as k_cg_update /
+// k_cg_pupdate, as k_cg_update_s80 / k_cg_pupdate_s80 with the scalar-register budget capped at 80 (stpcg.hip says
+// why), and as k_cg_update_ns / k_cg_update_ns_s80, the A-step of an odd iteration of the deferred-s form.  Textual inclusion, not a shared __device__ body: the first pair -- the single-GPU step -- must keep the exact
 // code it was tuned with.
 
 template <int PRE, bool FROM_SLOTS, int KC = 3, class FOLD = NoFold>
@@ -73,6 +73,11 @@ __global__ __launch_bounds__(kBlock) CG_KERNEL_ATTR void CG_UPDATE_NAME(size_t n
   const int mode = cs.mode;
   double acc[1] = {0};
   if (mode == CG_APPLY_SIGMA) {
+    // (CG_UPDATE_SIGMA 0 -- deferred-s form, odd iteration: s still lacks alpha_k-1 p_k-1, which has to go in FIRST; the
+    // direction kernel behind this one has the other direction buffer and applies both, stpcg.hip k_cg_pupdate_ds.  Decided
+    // where the file is included: a flag among the arguments, or a test of s, costs the instantiations that sit at 80
+    // SGPRs two more)
+    if (!CG_UPDATE_SIGMA) return;
     const double sigma = cs.sigma;
     for (size_t i = i0; i < n2; i += stride) {
       const double2 pv = reinterpret_cast<const double2 *>(p)[i];
