@@ -39,7 +39,9 @@ typedef enum mi_status {
   MI_ERR_OOM = 3,
   MI_ERR_NO_DEVICE = 4,
   MI_ERR_COMM = 5,
-  MI_ERR_INTERNAL = 6
+  MI_ERR_INTERNAL = 6,
+  MI_DECLINED = 7 /* not an error: the entry point does not take this call on the context as it is configured; nothing was
+                     done or counted, mi_last_error() names the cause, the caller keeps its own path (mi_stpcg_observed) */
 } mi_status;
 
 typedef struct mi_ctx mi_ctx;       /* device context: stream, memory pool, scalar file, communicator */
@@ -112,7 +114,7 @@ enum {
  * FORCE_LOCKSTEP, FORCE_UNIFORM_GRID, MAX_GRID, NO_DIRGRAM, DIRGRAM_DIRECT, IPC_TIMEOUT_MS, NO_FOLD, HALO_PUSH_LATE,
  * NO_PACKED, NO_WINDOW, NO_WIN_BOUNDS, NO_FAR_COMPUTED, WORDS16, NO_SPMM_STREAM, NO_SPMM_WIN, NO_UPDATE_MFMA,
  * NO_ZERO_COPY, NO_GRAM_HALF, NO_UPDATE_PAIR, SO3_NO_QUAT, SO3_NO_RQUAT, SO3_SORT_NBR, HALO_RPRIME, TWO_KERNEL_STEP, WIDE_QUAD,
- * NO_POLLED_SYNC, WARN_GENERIC, REANCHOR, NO_SPMM_SWEEP, SWEEP_ZSEGS, WIDE_WINDOW, EARLY_S, DEFER_S (DESIGN.md / INTEGRATION.md say what each selects).  For the boolean switches a value that
+ * NO_POLLED_SYNC, WARN_GENERIC, REANCHOR, NO_SPMM_SWEEP, SWEEP_ZSEGS, WIDE_WINDOW, EARLY_S, DEFER_S, NO_FUSED_OBSERVER (DESIGN.md / INTEGRATION.md say what each selects).  For the boolean switches a value that
  * is not an integer counts as 1 unless it is "no" / "false" / "off"; the integer-valued ones (MAX_GRID, IPC_TIMEOUT_MS,
  * WIDE_QUAD, WIDE_WINDOW, SO3_SORT_NBR, REANCHOR, SWEEP_ZSEGS) take integers only -- anything else is ignored with a warning and the default stays.  Any other
  * MI355OPT_* variable found in the environment (a removed or misspelt switch) gets one warning on stderr.  mi_ctx_set_option changes one on a live context (name with or without the MI355OPT_
@@ -289,14 +291,16 @@ enum {
   MI_STPCG_EXIT_RESIDUAL = 0, /* :290 */
   MI_STPCG_EXIT_MAXIT = 1,    /* :285 loop exhausted */
   MI_STPCG_EXIT_KERNEL = 2,   /* :305-337 */
-  MI_STPCG_EXIT_BOUNDARY = 3  /* :347-361 */
+  MI_STPCG_EXIT_BOUNDARY = 3, /* :347-361 */
+  MI_STPCG_EXIT_USER = 4      /* :365-369, the observer of mi_stpcg_observed said stop */
 };
 
 typedef struct mi_stpcg_result {
   double update_step_M_norm; /* :334,359,424 */
   size_t num_iterations;     /* :285 (not incremented on boundary exits) */
   int exit_reason;
-  size_t hvp_calls;          /* operator applications enqueued (incl. speculative ones past the exit) */
+  size_t hvp_calls;          /* operator applications ENQUEUED (incl. speculative ones past the exit: it depends on when the
+                                host saw the exit and may differ by a few between runs, by one in an observed solve) */
   double rv_final;           /* last <r,v> */
   int precon_status;         /* 0, or 2: a constraint preconditioner's inner iteration stopped at its iteration limit short
                                 of its tolerance during this solve (an INEXACT projection; mi_precon_constraint_info has
@@ -314,6 +318,42 @@ MI_API void mi_stpcg_default_params(mi_stpcg_params *p);
 MI_API int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P /*nullable*/,
                     const mi_stpcg_params *params, mi_vec *s_out, mi_stpcg_result *result,
                     mi_stpcg_trace *trace /*nullable*/);
+/* The same solve with the reference's STPCGUserFunction (IterativeSolvers.h:50-59) as a C callback: logging, custom
+ * stopping rules, time limits inside the inner solve.  The observer is called once per pass after alpha_k is known and
+ * the boundary tests have passed, before any update (:365-369) -- not in a pass that leaves by the kernel-of-H or the
+ * boundary exit, as in the reference.  s, r, v, p are read-only views owned by the solve, valid for the duration of the
+ * call: the step so far, the model gradient g + H s, the preconditioned residual (v == r, the same handle, when there is
+ * no preconditioner, :231) and the direction; k is the number of completed updates.  A non-zero return stops the solve
+ * like the reference's `break` (:369): s_out stays s_k, update_step_M_norm = sqrt(s_M_s) (:424), num_iterations = k,
+ * exit_reason = MI_STPCG_EXIT_USER.
+ *   Contract.  The observer runs on the calling thread with the stream drained up to this pass's operator.  On the same
+ * context it may call the read-only vector functions on the views (mi_vec_dot, mi_vec_dot_batch, mi_vec_download,
+ * mi_vec_copy FROM a view) and the plain applications mi_op_apply(H, view, own vector) / mi_precon_apply(P, view, own
+ * vector) of the solve's operator and of an ordinary (diagonal, block, callback, Stiefel) preconditioner -- e.g. for the
+ * model value <g,s> + <s,Hs>/2: the plain application of every built-in operator leaves the partial rows alone that
+ * k_cg_update still has to reduce after the observer returns, and a user operator's plain callback (mi_apply_fn) is not
+ * given them.  It must not write or destroy the views, must not apply a constraint preconditioner (its status word and
+ * multipliers belong to the running solve), and must not call anything else that computes on that context: mi_stpcg /
+ * mi_stpcg_observed are refused with MI_ERR_INVALID_ARGUMENT; mi_lsqr, the LOBPCG building blocks, the *_model / *_trial
+ * chains and everything built on them (TNT, TNLS, GradientDescent) are NOT checked and share the reduction buffers and
+ * the scalar file with the running solve.  A C++ exception must not leave it.
+ *   What runs.  The kernels of mi_stpcg -- operator pass with fused dots, k_cg_update, k_cg_pupdate, direction-Gram
+ * recurrence and its re-anchoring, every preconditioner kind incl. constraint_At -- and the same bits: with an observer
+ * that never stops, s_out, the result and the trace equal mi_stpcg's.  What differs: no run-ahead (run_ahead is
+ * ignored).  Between the operator and k_cg_update of every pass a one-workgroup kernel re-reduces the three curvature
+ * sums, repeats the scalar step on a copy of the state and hands {alpha_k, decision} to the host through pinned words
+ * and the polled flag: one small kernel and one polled wait per pass (mi_ctx_sync_count rises by one per pass; kernel
+ * timing id MI_K_CG_SCALAR_A).  DEFER_S, EARLY_S, TWO_KERNEL_STEP and params->defer_result are off for an observed solve.
+ *   Returns MI_DECLINED -- nothing done, nothing counted -- on a context that is one of several ranks or completes its
+ * reductions through an exchange layer, with MI355OPT_FORCE_LOCKSTEP / FORCE_SLOT_PATH, and with MI355OPT_NO_FUSED_OBSERVER=1
+ * (the A/B switch of the template layer): the caller keeps its generic loop. */
+/* the small query behind that: MI_OK, or MI_DECLINED with *why (nullable) pointing at a literal that names the cause */
+MI_API int mi_stpcg_observer_available(mi_ctx *ctx, const char **why);
+typedef int (*mi_stpcg_observer)(void *user, size_t k, const mi_vec *s, const mi_vec *r, const mi_vec *v,
+                                 const mi_vec *p, double alpha);
+MI_API int mi_stpcg_observed(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P /*nullable*/,
+                             const mi_stpcg_params *params, mi_stpcg_observer fn, void *user, mi_vec *s_out,
+                             mi_stpcg_result *result, mi_stpcg_trace *trace /*nullable*/);
 /* Result of the last mi_stpcg call made with defer_result on this context (update_step_M_norm :334,359,424,
  * num_iterations :285, exit reason, last <r,v>).  Waits only if the state copy enqueued at the solve's exit has not
  * completed yet -- after any later read-back on the same context it has.  (trace is not available in deferred mode.) */

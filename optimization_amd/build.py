@@ -137,7 +137,8 @@ def build_harness(force=False):
     the headers stay compilable by hipcc's front end):
       tests/cpp/libharness_host.so    templates on a host vector, same driver code as the real
                                       reference build (oracle/template_driver.inc)
-      tests/cpp/libharness_device.so  templates on MI355::DeviceVector, linked to libmi355opt.so"""
+      tests/cpp/libharness_device.so  templates on MI355::DeviceVector, linked to libmi355opt.so
+      tests/cpp/libharness_observer.so  STPCG with a user function on both vector types (one driver)"""
     tdir = os.path.join(ROOT, "tests", "cpp")
     inc = ["-I", os.path.join(HERE, "include"), "-I", os.path.join(ROOT, "oracle")]
     common = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-type-limits"]
@@ -168,6 +169,17 @@ def build_harness(force=False):
             if r.returncode != 0:
                 raise RuntimeError("clang front-end check of the template layer failed:\n" + r.stderr[-6000:])
     out.append(dev_so)
+    # tests/cpp/harness_observer.cpp: STPCG with a user function, one templated driver on the host vector (generic loop)
+    # and on DeviceVector (fused observed solve, mi_stpcg_observed)
+    ob_src = os.path.join(tdir, "harness_observer.cpp")
+    ob_so = os.path.join(tdir, "libharness_observer.so")
+    if force or _newer(ob_src, ob_so, hdrs + [LIB]):
+        cmd = common + inc + ["-I", os.path.join(ROOT, "include"), ob_src, "-o", ob_so, "-L", HERE,
+                              "-lmi355opt", "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib"]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("observer harness build failed:\n" + r.stderr[-6000:])
+    out.append(ob_so)
     # tests/cpp/harness_sinfit.hip: the reference's TNLS sin-fit problem with HIP kernels of its own (hipcc)
     sf_src = os.path.join(tdir, "harness_sinfit.hip")
     sf_so = os.path.join(tdir, "libharness_sinfit.so")

@@ -14,13 +14,13 @@ LIB_PATH = os.environ.get("MI355OPT_LIB") or os.path.join(_HERE, "libmi355opt.so
 
 MI_OK = 0
 STATUS = {0: "MI_OK", 1: "MI_ERR_INVALID_ARGUMENT", 2: "MI_ERR_HIP", 3: "MI_ERR_OOM",
-          4: "MI_ERR_NO_DEVICE", 5: "MI_ERR_COMM", 6: "MI_ERR_INTERNAL"}
+          4: "MI_ERR_NO_DEVICE", 5: "MI_ERR_COMM", 6: "MI_ERR_INTERNAL", 7: "MI_DECLINED"}
 KERNELS = ["none", "cg_init", "cg_dot3", "cg_scalar_a", "cg_update", "cg_scalar_b", "cg_pupdate",
            "csr_spmm", "stiefel_spmm_gram", "stiefel_gram_reduce", "stiefel_finish_dots",
            "stiefel_retract", "bsr3_spmv_dots", "blas1", "lobpcg_gram", "lobpcg_update",
            "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo"]
 KID = {k: i for i, k in enumerate(KERNELS)}
-STPCG_EXIT = ["RESIDUAL", "MAXIT", "KERNEL", "BOUNDARY"]
+STPCG_EXIT = ["RESIDUAL", "MAXIT", "KERNEL", "BOUNDARY", "USER"]
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -29,6 +29,8 @@ c_size_p = C.POINTER(C.c_size_t)
 vp = C.c_void_p
 
 APPLY_FN = C.CFUNCTYPE(C.c_int, vp, vp, vp)
+# mi_stpcg_observer: (user, k, s, r, v, p, alpha) -> nonzero stops the solve
+OBSERVER_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, C.c_double)
 
 
 class PanelBlocks(C.Structure):
@@ -173,6 +175,9 @@ def load():
         "mi_precon_destroy": [vp],
         "mi_stpcg": [vp, vp, vp, vp, C.POINTER(StpcgParams), vp, C.POINTER(StpcgResult),
                      C.POINTER(StpcgTrace)],
+        "mi_stpcg_observed": [vp, vp, vp, vp, C.POINTER(StpcgParams), OBSERVER_FN, vp, vp, C.POINTER(StpcgResult),
+                              C.POINTER(StpcgTrace)],
+        "mi_stpcg_observer_available": [vp, C.POINTER(C.c_char_p)],
         "mi_stiefel_gram": [vp, C.c_size_t, C.c_int, vp, vp, c_double_p],
         "mi_stiefel_project": [vp, C.c_size_t, C.c_int, vp, vp, vp],
         "mi_stiefel_retract": [vp, C.c_size_t, C.c_int, vp, vp, vp],
@@ -504,9 +509,14 @@ class Context:
 
     # fused STPCG ------------------------------------------------------------------------------
     def stpcg(self, g, H, P=None, Delta=1.0, max_iterations=1000, kappa_fgr=.1, theta=.5,
-              epsilon=1e-8, run_ahead=0, trace_cap=0, s_out=None, defer=False, constraint_At=False):
+              epsilon=1e-8, run_ahead=0, trace_cap=0, s_out=None, defer=False, constraint_At=False, observer=None):
         """defer=True: mi_stpcg returns without waiting for the device (s is valid in stream order); the scalar
-        results come from stpcg_collect()."""
+        results come from stpcg_collect().
+        observer: callable (k, s, r, v, p, alpha) -> bool, the reference's STPCGUserFunction (mi_stpcg_observed): called
+        once per pass after alpha_k is known and before any update; s, r, v, p are non-owning Vec wrappers of the
+        solve's own storage, valid for the duration of the call only (read them; v is r itself without a
+        preconditioner); a true return stops the solve with s as it is (exit_reason 4).  An exception raised in it
+        stops the solve and is re-raised here after the library call has returned."""
         prm = StpcgParams(Delta, max_iterations, kappa_fgr, theta, epsilon, run_ahead, int(constraint_At),
                           int(defer))
         res = StpcgResult()
@@ -517,8 +527,27 @@ class Context:
             arrs = {k: np.zeros(trace_cap) for k in ("alpha", "beta", "kappa", "rv")}
             tr = StpcgTrace(trace_cap, 0, _dp(arrs["alpha"]), _dp(arrs["beta"]), _dp(arrs["kappa"]),
                             _dp(arrs["rv"]))
-        check(self.L.mi_stpcg(self.h, g.h, H.h, P.h if P is not None else None, C.byref(prm), s.h,
-                              C.byref(res), C.byref(tr) if tr else None))
+        if observer is not None:
+            if defer:
+                raise ValueError("an observed solve has no deferred result")
+            raised = []
+
+            def tramp(_user, k, sh, rh, vh, ph, alpha):
+                try:
+                    vs = [Vec(self, 0, handle=vp(h)) for h in (sh, rh, vh, ph)]
+                    return 1 if observer(int(k), vs[0], vs[1], vs[2], vs[3], float(alpha)) else 0
+                except BaseException as e:  # noqa: nothing may propagate through the C frames
+                    raised.append(e)
+                    return 1
+            cfn = OBSERVER_FN(tramp)
+            st = self.L.mi_stpcg_observed(self.h, g.h, H.h, P.h if P is not None else None, C.byref(prm), cfn, None,
+                                          s.h, C.byref(res), C.byref(tr) if tr else None)
+            if raised:
+                raise raised[0]
+            check(st)
+        else:
+            check(self.L.mi_stpcg(self.h, g.h, H.h, P.h if P is not None else None, C.byref(prm), s.h,
+                                  C.byref(res), C.byref(tr) if tr else None))
         out = dict(s=s, M_norm=res.update_step_M_norm, iterations=res.num_iterations,
                    exit_reason=res.exit_reason, hvp_calls=res.hvp_calls, rv_final=res.rv_final,
                    precon_status=res.precon_status)

@@ -141,6 +141,8 @@ struct Config {
   bool defer_s = true;              // DEFER_S: the single-context solve with the flat direction kernel adds the step up every SECOND
                                     // iteration, s = (s + alpha_k p_k) + alpha_k+1 p_k+1, from two alternating direction buffers
                                     // (k_cg_pupdate_ds; same bits, 4.5 N instead of 5 N doubles per iteration); 0: every iteration
+  bool no_fused_observer = false;   // NO_FUSED_OBSERVER: mi_stpcg_observed declines (MI_DECLINED) and STPCG with a user function on
+                                    // MI355::DeviceVector runs the generic loop, one kernel per vector statement (A/B)
   bool so3_no_rquat = false;        // SO3_NO_RQUAT: the SO(3)^N model assembly gathers the neighbours' rotations as 72-byte matrices
                                     // (r05 form) instead of 32-byte quaternions written by the retraction (r06; creation-time)
   bool so3_no_quat = false;         // SO3_NO_QUAT: the measurements of mi_so3n stay 3 x 3 matrices (r04 form; creation-time)
@@ -187,6 +189,7 @@ struct mi_ctx {
   hipEvent_t cg_deferred_ev = nullptr;
   bool cg_deferred = false;
   size_t cg_deferred_hvp = 0;
+  bool cg_in_observer = false;      // mi_stpcg_observed is inside its observer: no solve may start on this context
   unsigned long long cg_deferred_seq = 0;  // polled form of the deferred result (0: the event form)
   mi::HostStatus *status = nullptr;      // pinned, device-visible
   mi::HostStatus *status_dev = nullptr;  // device pointer of the same memory

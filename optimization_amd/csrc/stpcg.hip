@@ -959,6 +959,51 @@ __global__ __launch_bounds__(kBlock) void k_cg_gdir_anchor(const double *__restr
   if (dst2 && threadIdx.x < ns) dst2[threadIdx.x] = slots[ns + threadIdx.x];
 }
 
+// OBSERVED SOLVE (mi_stpcg_observed): the reference's user function (IterativeSolvers.h:50-59) is called once per pass
+// after alpha_k is known and the boundary tests have passed, before any update (:365-369).  In the fused step that is
+// the moment between the operator pass and k_cg_update: s += alpha p of the LAST pass has been applied (it lives in the
+// direction kernel), nothing of THIS pass has, and alpha_k with every branch decision of :300-362 follows from the
+// three curvature sums the operator left as partial rows.  k_cg_peek tells the host: ONE workgroup re-reduces components
+// 0..2 of those rows with the consumers' own reduce_rows (component by component, fixed order: the consumers' totals bit
+// for bit, whatever else their rows carry), runs step_a on a COPY of the live state and stores
+//   {mode on entry, mode after step_a, alpha, k}
+// into pinned host words, the context's polled flag behind them.  The live state is not written: k_cg_update repeats
+// step_a from the same rows as in every other solve -- its instantiations, and the un-observed solve, are untouched.
+__global__ __launch_bounds__(kBlock) void k_cg_peek(CgConst cc, const CgState *__restrict__ st,
+                                                    const double *__restrict__ partials_a, int nparts_a,
+                                                    unsigned long long *host, unsigned long long *flag,
+                                                    unsigned long long seq) {
+  __shared__ double lds[3 * (kWaves + 1)];
+  CgState cs = load_state(st);
+  const int mode_in = cs.mode;
+  if (mode_in == CG_RUN) {  // (the same in every thread: the barriers of the reduction are uniform)
+    double d[3];
+    reduce_rows<3>(partials_a, nparts_a, d, lds);
+    step_a(cs, cc, d[0], d[1], d[2]);
+  }
+  if (threadIdx.x != 0) return;
+  host[0] = (unsigned long long)mode_in;
+  host[1] = (unsigned long long)cs.mode;
+  reinterpret_cast<double *>(host)[2] = cs.alpha;
+  host[3] = cs.k;
+  __threadfence_system();
+  if (flag) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// the observer said stop: the reference's `break` at :369 -- |s|_M from the recurrence (:424), k completed updates, and
+// nothing of this pass in s, r or p.  One thread, in place: no kernel of the solve is in flight beside it.
+__global__ void k_cg_user_stop(CgState *st, HostStatus *hs) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  CgState cs = load_state(st);
+  if (cs.mode != CG_RUN) return;
+  cs.M_norm = sqrt(cs.sk_M_2);  // :424
+  cs.exit_reason = MI_STPCG_EXIT_USER;
+  cs.mode = CG_DONE;
+  store_state(st, cs);
+  publish(hs, cs.launches, 1);
+}
+
 inline void cpu_relax() { __builtin_ia32_pause(); }
 
 }  // namespace
@@ -1066,13 +1111,26 @@ int mi_stpcg_collect(mi_ctx *ctx, mi_stpcg_result *result) {
   return precon_fail_check(ctx, result);
 }
 
-int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpcg_params *prm,
-             mi_vec *s_out, mi_stpcg_result *result, mi_stpcg_trace *trace) {
+// mi_stpcg (observer == nullptr) and mi_stpcg_observed share this body; every `observed` below is false for the former,
+// which enqueues exactly what it always did
+static int stpcg_solve(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpcg_params *prm,
+                       mi_stpcg_observer observer, void *observer_user, mi_vec *s_out, mi_stpcg_result *result,
+                       mi_stpcg_trace *trace) {
   MI_REQUIRE(ctx && g && H && prm && s_out && result, "null argument");
   MI_REQUIRE(g->ctx == ctx && s_out->ctx == ctx && H->ctx == ctx, "objects belong to another context");
   MI_REQUIRE(g->n == s_out->n && g->n == H->n, "dimension mismatch: g %zu, s %zu, H %zu", g->n,
              s_out->n, H->n);
   MI_REQUIRE(g->d != s_out->d, "g and s_out must not alias");
+  MI_REQUIRE(!ctx->cg_in_observer, "a solve was started on this context from inside an STPCG observer");
+  const bool observed = observer != nullptr;
+  if (observed) {
+    // nothing has been touched or counted yet: the caller keeps its own loop
+    const char *why = nullptr;
+    if (mi_stpcg_observer_available(ctx, &why) != MI_OK) {
+      set_error("mi_stpcg_observed declined: %s", why);
+      return MI_DECLINED;
+    }
+  }
   touch(s_out);
   ctx->fusion.fused_stpcg_solves++;
   MI_REQUIRE(!P || (P->ctx == ctx && P->n == g->n), "preconditioner dimension/context mismatch");
@@ -1183,14 +1241,17 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
   const bool init_fused = recur && n == dgp->n * (size_t)dgp->p;
   const bool gdir_in_scalar_init = recur && !sharded && !rows;
   // opt-in experiment: the two-kernel step (k_cg_step2; one rank, Stiefel(n,3) in the window form)
+  // (an observed solve keeps the plain three-kernel step: the two-kernel step has no point between the operator and
+  // the update, the early-s form is an experiment, and the deferred-s form would show the observer of an odd pass an s
+  // that is one term short)
   const bool twok = ctx->cfg.two_kernel_step && recur && dgp->twok && dgp->p == 3 && !sharded && !rows && !lockstep &&
-                    init_fused && gdir_in_scalar_init;
+                    init_fused && gdir_in_scalar_init && !observed;
   // (the early-s form: single context, v = r or any plain vector, at most three elements per thread, <= 512 rows)
   const bool early = !sharded && !rows && sp == 0 && ctx->cfg.early_s && grid <= 512 &&
-                     cc.rag0 <= 2ull * (size_t)grid * kBlock && (n >> 1) < ((size_t)1 << 31);
+                     cc.rag0 <= 2ull * (size_t)grid * kBlock && (n >> 1) < ((size_t)1 << 31) && !observed;
   // deferred-s form (k_cg_pupdate_ds): single context, flat direction kernel; the direction lives in two buffers that
   // swap every iteration -- `p` is the current one wherever this function names it
-  const bool defer = !sharded && !rows && !lockstep && !twok && sp == 0 && !early && ctx->cfg.defer_s;
+  const bool defer = !sharded && !rows && !lockstep && !twok && sp == 0 && !early && ctx->cfg.defer_s && !observed;
   CgState *st_final = st0;
   double *tr = tcap ? ctx->trace_dev : nullptr;
   int ret = MI_OK;
@@ -1205,6 +1266,20 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
     }
   }
   ctx->cg_live = st0;
+  // observed solve: k_cg_peek's four words land at the head of the pinned state copy (free until the final read-back)
+  unsigned long long *peek_dev = nullptr;
+  if (observed) {
+    const hipError_t e = hipHostGetDevicePointer((void **)&peek_dev, ctx->cg_host, 0);
+    if (e != hipSuccess) {
+      mi_vec_destroy(r);
+      mi_vec_destroy(p);
+      mi_vec_destroy(p2);
+      mi_vec_destroy(Hp);
+      mi_vec_destroy(v);
+      ctx->cg_live = nullptr;
+      return hip_fail(e, "stpcg observer: device address of the pinned words", __FILE__, __LINE__);
+    }
+  }
 
 #define CG_CHECK(expr)   \
   do {                   \
@@ -1297,10 +1372,11 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
   // --- main loop: speculative enqueue with bounded run-ahead -----------------------------------
   {
     size_t hvp = 0;
+    bool observed_last_pass = false;
     for (size_t k = 0; k < prm->max_iterations; ++k) {
       // throttle: at most run_ahead launches ahead of the device
       uint64_t w = ctx->status->word;
-      while (!(w & 1) && k > (w >> 1) + (uint64_t)run_ahead) {
+      while (!observed && !(w & 1) && k > (w >> 1) + (uint64_t)run_ahead) {  // (an observed solve never runs ahead)
         cpu_relax();
         w = ctx->status->word;
       }
@@ -1374,6 +1450,44 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
         CG_CHECK(launch_dot3_partials(ctx, n, p->d, Hp->d, &nparts));
       }
       ++hvp;
+      if (observed) {
+        // alpha_k and the decisions of :300-362 to the host: one small kernel and one polled wait per pass
+        ctx->host_syncs++;
+        unsigned long long *flag = nullptr;
+        const unsigned long long seq = poll_begin(ctx, &flag);
+        {
+          KScope ks(ctx, MI_K_CG_SCALAR_A);
+          hipLaunchKernelGGL(k_cg_peek, dim3(1), dim3(kBlock), 0, st, cc, (const CgState *)st0,
+                             (const double *)ctx->partials, nparts, peek_dev, seq ? flag : (unsigned long long *)nullptr,
+                             seq);
+        }
+        {
+          hipError_t e = hipGetLastError();
+          if (e != hipSuccess) CG_CHECK(hip_fail(e, "stpcg observer peek launch", __FILE__, __LINE__));
+        }
+        CG_CHECK(poll_finish(ctx, seq, "stpcg observer peek"));
+        const volatile unsigned long long *pk = reinterpret_cast<const volatile unsigned long long *>(ctx->cg_host);
+        const int mode_in = (int)pk[0], mode_a = (int)pk[1];
+        // (this pass's operator is already enqueued -- hvp_calls counts ENQUEUED passes, here as in the un-observed solve --
+        // unless the test of the status word at the top of the loop happened to see the exit first)
+        if (mode_in == CG_DONE) break;  // the last pass's B-step (or the initialisation) ended the solve: :285, :290
+        if (mode_a == CG_RUN) {
+          double alpha_k;
+          const unsigned long long abits = pk[2];
+          memcpy(&alpha_k, &abits, sizeof(alpha_k));
+          ctx->cg_in_observer = true;
+          const int stop = observer(observer_user, (size_t)pk[3], s_out, r, v ? v : r, p, alpha_k);
+          ctx->cg_in_observer = false;
+          if (stop) {
+            hipLaunchKernelGGL(k_cg_user_stop, dim3(1), dim3(64), 0, st, st0, ctx->status_dev);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) CG_CHECK(hip_fail(e, "stpcg observer stop launch", __FILE__, __LINE__));
+            break;
+          }
+        } else {
+          observed_last_pass = true;  // kernel-of-H or boundary exit inside this pass: the reference does not call either
+        }
+      }
       // (deferred-s form, odd k: a term of s is pending, and a boundary step is the direction kernel's to apply behind it)
       const bool sigma_later = defer && (k & 1);
 #define UPD_ARGS                                                                                      \
@@ -1506,13 +1620,14 @@ int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpc
 #undef LAUNCH_PUPD
 #undef PUPD
 #undef PUPD_ARGS
+      if (observed_last_pass) break;  // (the pass just enqueued ends the solve: no further peek)
     }
     result->hvp_calls = hvp;
     comm_halo_fold_drop(ctx);  // (a push behind the last enqueued iteration has no reader)
   }
 
   // --- read back the final state ----------------------------------------------------------------
-  if (prm->defer_result && !(trace && trace->cap)) {
+  if (prm->defer_result && !(trace && trace->cap) && !observed) {
     // the copy travels behind the solve; whoever waits for the stream next (or mi_stpcg_collect) completes it
     hipError_t e = hipSuccess;
     *precon_fail_host(ctx) = 0.0;
@@ -1589,6 +1704,28 @@ cleanup:
   mi_vec_destroy(Hp);
   mi_vec_destroy(v);
   return ret;
+}
+
+int mi_stpcg_observer_available(mi_ctx *ctx, const char **why) {
+  MI_REQUIRE(ctx, "null argument");
+  const char *w = nullptr;  // (literals: they outlive the call)
+  if (ctx->cfg.no_fused_observer) w = "MI355OPT_NO_FUSED_OBSERVER is set";
+  else if (ctx->world_size > 1) w = "the context is one of several ranks";
+  else if (ctx->force_lockstep) w = "MI355OPT_FORCE_LOCKSTEP is set";
+  else if (slot_mode(ctx) || rows_mode(ctx)) w = "the context completes its reductions through an exchange layer";
+  if (why) *why = w ? w : "";
+  return w ? MI_DECLINED : MI_OK;
+}
+
+int mi_stpcg(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpcg_params *prm, mi_vec *s_out,
+             mi_stpcg_result *result, mi_stpcg_trace *trace) {
+  return stpcg_solve(ctx, g, H, P, prm, nullptr, nullptr, s_out, result, trace);
+}
+
+int mi_stpcg_observed(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpcg_params *prm,
+                      mi_stpcg_observer fn, void *user, mi_vec *s_out, mi_stpcg_result *result, mi_stpcg_trace *trace) {
+  MI_REQUIRE(fn, "mi_stpcg_observed: null observer (mi_stpcg is the solve without one)");
+  return stpcg_solve(ctx, g, H, P, prm, fn, user, s_out, result, trace);
 }
 
 }  // extern "C"

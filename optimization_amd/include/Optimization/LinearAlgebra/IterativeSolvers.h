@@ -11,14 +11,17 @@
 // reference compiled from its own headers).  When Vector is MI355::DeviceVector and the callables
 // are the tagged device function objects of Optimization/MI355/Device.h, STPCG hands the whole loop
 // to the fused HIP implementation (mi_stpcg: 4 streaming kernels per iteration, device-resident
-// scalars, no host read-back inside the loop); every other combination runs the generic loop below
-// through the Vector's operators.
+// scalars, no host read-back inside the loop).  A user function keeps that loop (mi_stpcg_observed:
+// the same kernels, plus one small kernel and one polled wait per pass that bring alpha_k to the host;
+// context switch NO_FUSED_OBSERVER restores the generic loop).  Every other combination runs the
+// generic loop below through the Vector's operators.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <limits>
+#include <exception>
 #include <optional>
 #include <stdexcept>
 #include <tuple>
@@ -39,6 +42,9 @@ namespace LinearAlgebra {
 
 // Observer invoked once per completed STPCG pass, after alpha_k is known and before the update is
 // applied; returning true stops the solver with s_k un-updated.   (reference :50-59, :365-369)
+// On MI355::DeviceVector with the tagged callables the vectors it receives are views of the fused
+// solver's own storage, valid during the call: read them (dot, to_host, copy), do not write them, and
+// do not start another solve on the same context from inside.
 template <typename Vector, typename Multiplier, typename Scalar = double, typename... Args>
 using STPCGUserFunction = std::function<bool(
     size_t k, const Vector &g, const SymmetricLinearOperator<Vector, Args...> &H,
@@ -67,6 +73,7 @@ bool stpcg_on_device(const Vector &g, const SymmetricLinearOperator<Vector, Args
                      const InnerProduct<Vector, Scalar, Args...> &inner_product,
                      const std::optional<STPCGPreconditioner<Vector, Multiplier, Args...>> &P,
                      const std::optional<LinearOperator<Multiplier, Vector, Args...>> &At,
+                     const std::optional<STPCGUserFunction<Vector, Multiplier, Scalar, Args...>> &user_function,
                      Scalar Delta, size_t max_iterations, Scalar kappa_fgr, Scalar theta, Scalar epsilon,
                      Vector &s_out, Scalar &update_step_M_norm, size_t &num_iterations, const char *&why) {
   // `why`: which probe sent the solve to the generic loop (reported through mi_ctx_note_generic by the caller)
@@ -124,6 +131,46 @@ bool stpcg_on_device(const Vector &g, const SymmetricLinearOperator<Vector, Args
     DeferScope *defer = DeferScope::active();
     prm.defer_result = defer ? 1 : 0;
     mi_stpcg_result res;
+    if (user_function) {
+      // (multi-rank / exchange-layer contexts and the A/B switch NO_FUSED_OBSERVER: the generic loop, and why)
+      const char *declined = nullptr;
+      if (mi_stpcg_observer_available(g.context(), &declined) != MI_OK) return no(declined);
+      s_out = DeviceVector::like(g);
+      // the user function observes the fused solve (mi_stpcg_observed): the four handles as non-owning DeviceVectors,
+      // the caller's own g, H, P, At.  An exception must not cross the C ABI: it stops the solve and is rethrown here,
+      // after the library has read back and cleaned up.
+      struct Trampoline {
+        const STPCGUserFunction<Vector, Multiplier, Scalar, Args...> &fn;
+        const Vector &g;
+        const SymmetricLinearOperator<Vector, Args...> &H;
+        const std::optional<STPCGPreconditioner<Vector, Multiplier, Args...>> &P;
+        const std::optional<LinearOperator<Multiplier, Vector, Args...>> &At;
+        std::exception_ptr thrown;
+        static int call(void *user, size_t k, const mi_vec *s, const mi_vec *r, const mi_vec *v, const mi_vec *p,
+                        double alpha) {
+          Trampoline &t = *static_cast<Trampoline *>(user);
+          try {
+            mi_ctx *c = t.g.context();
+            const DeviceVector sk = DeviceVector::view(c, const_cast<mi_vec *>(s));
+            const DeviceVector rk = DeviceVector::view(c, const_cast<mi_vec *>(r));
+            const DeviceVector vk = DeviceVector::view(c, const_cast<mi_vec *>(v));
+            const DeviceVector pk = DeviceVector::view(c, const_cast<mi_vec *>(p));
+            return t.fn(k, t.g, t.H, t.P, t.At, sk, rk, vk, pk, alpha) ? 1 : 0;
+          } catch (...) {
+            t.thrown = std::current_exception();
+            return 1;
+          }
+        }
+      } tramp{*user_function, g, H, P, At, nullptr};
+      prm.defer_result = 0;
+      const int st = mi_stpcg_observed(g.context(), g.handle(), dop->op, prec, &prm, &Trampoline::call, &tramp,
+                                       s_out.handle(), &res, nullptr);
+      if (tramp.thrown) std::rethrow_exception(tramp.thrown);
+      check(st);
+      update_step_M_norm = res.update_step_M_norm;
+      num_iterations = res.num_iterations;
+      return true;
+    }
     s_out = DeviceVector::like(g);
     check(mi_stpcg(g.context(), g.handle(), dop->op, prec, &prm, s_out.handle(), &res, nullptr));
     if (defer) defer->taken_on(g.context());
@@ -217,15 +264,11 @@ Vector STPCG(const Vector &g, const SymmetricLinearOperator<Vector, Args...> &H,
   if constexpr (MI355::is_device_vector<Vector>::value) {
     const char *why = "extra arguments (Args...) are passed to the callables";
     if constexpr (sizeof...(Args) == 0) {
-      if (!user_function) {
-        Vector s_dev;
-        if (detail::stpcg_on_device<Vector, Multiplier, Scalar>(g, H, inner_product, P, At, Delta, max_iterations,
-                                                                kappa_fgr, theta, epsilon, s_dev,
-                                                                update_step_M_norm, num_iterations, why))
-          return s_dev;
-      } else {
-        why = "a user function is supplied (it observes every iteration's vectors)";
-      }
+      Vector s_dev;
+      if (detail::stpcg_on_device<Vector, Multiplier, Scalar>(g, H, inner_product, P, At, user_function, Delta,
+                                                              max_iterations, kappa_fgr, theta, epsilon, s_dev,
+                                                              update_step_M_norm, num_iterations, why))
+        return s_dev;
     }
     // the generic loop below on device vectors: make the fall observable (mi_ctx_fusion_counters, MI355OPT_WARN_GENERIC)
     if (!g.empty()) (void)mi_ctx_note_generic(g.context(), MI_GENERIC_STPCG, why);
