@@ -581,6 +581,9 @@ MI_API int mi_comm_kernel_launches(mi_ctx *ctx, unsigned long long out[4]);
  * stride D when every entry outside the window is at row +- D (the kernels then compute those columns, halo columns
  * of a row shard included) else 0, halo rows} */
 MI_API int mi_debug_csr_window_info(const mi_csr *A, size_t out[4]);
+/* read-only: the forms an SO(3)^N problem took -- {measurements stored as unit quaternions, neighbours gathered as
+ * quaternions, slices, incidences, padded incidence slots, workgroups of the model assembly}; needs no GPU work */
+MI_API int mi_debug_so3n_info(const mi_so3n *q, size_t out[6]);
 /* host-only: the run plan of the LDS-window kernels (first tile of every run + the end) for `ntiles` tiles of 256 rows,
  * a workgroup budget, a CU count and the matrix's far stride in rows (0: none); needs no GPU */
 MI_API int mi_debug_window_runs(int ntiles, int max_wgs, int num_cu, size_t far_stride, int *bounds_out, int cap,

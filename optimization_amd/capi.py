@@ -229,6 +229,7 @@ def load():
         "mi_comm_kernel_launches": [vp, C.POINTER(C.c_ulonglong)],
         "mi_comm_ipc_fold": [vp, C.c_int],
         "mi_debug_csr_window_info": [vp, c_size_p],
+        "mi_debug_so3n_info": [vp, c_size_p],
         "mi_debug_time_fused_apply": [vp, vp, vp, C.c_int, c_double_p],
         "mi_debug_set_rank": [vp, C.c_int, C.c_int],
         "mi_debug_csr_set_halo": [vp, C.c_int, c_double_p],
@@ -1051,6 +1052,13 @@ class So3N:
         Y = Vec(self.ctx, 9 * self.N)
         check(self.L.mi_so3n_retract(self.h, R.h, xi.h, Y.h))
         return Y
+
+    def info(self):
+        """mi_debug_so3n_info: dict(sinc_quat, gather_quat, nslices, nnzb, padded, model_grid)"""
+        out = (C.c_size_t * 6)()
+        check(self.L.mi_debug_so3n_info(self.h, out))
+        return dict(sinc_quat=bool(out[0]), gather_quat=bool(out[1]), nslices=int(out[2]), nnzb=int(out[3]),
+                    padded=int(out[4]), model_grid=int(out[5]))
 
     def trial(self, R, h, g, with_precon=True):
         """mi_so3n_trial: (R_trial Vec, dict(f, hh, gh, hHh, grad_sqnorm, precon_grad_sqnorm))"""

@@ -647,6 +647,20 @@ int mi_so3n_destroy(mi_so3n *q) {
   return MI_OK;
 }
 
+// Read-only: which forms this problem took.  out = {measurements as unit quaternions (sinc_quat), neighbours gathered as
+// quaternions (Rq), slices, incidences, padded incidence slots, workgroups of the model assembly (fewer than
+// ceil(slices / 4): the grid-stride walk)}.  No GPU work (tests/test_gpu_so3n_edges.py).
+int mi_debug_so3n_info(const mi_so3n *q, size_t out[6]) {
+  MI_REQUIRE(q && out, "null argument");
+  out[0] = q->sinc_quat ? 1 : 0;
+  out[1] = q->Rq ? 1 : 0;
+  out[2] = q->nslices;
+  out[3] = q->nnzb;
+  out[4] = q->padded;
+  out[5] = (size_t)model_grid(q);
+  return MI_OK;
+}
+
 int mi_so3n_objective(mi_so3n *q, const mi_vec *R, double *f) {
   MI_REQUIRE(q && R && f, "null argument");
   MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
