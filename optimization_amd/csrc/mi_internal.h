@@ -58,6 +58,30 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
     }                                      \
   } while (0)
 
+// ---- launch helpers (dispatch on p): the statement runs with P as a compile-time constant -----
+#define DISPATCH_P(p, ...)                                          \
+  switch (p) {                                                      \
+    case 1: { constexpr int P = 1; __VA_ARGS__; } break;            \
+    case 2: { constexpr int P = 2; __VA_ARGS__; } break;            \
+    case 3: { constexpr int P = 3; __VA_ARGS__; } break;            \
+    case 4: { constexpr int P = 4; __VA_ARGS__; } break;            \
+    case 5: { constexpr int P = 5; __VA_ARGS__; } break;            \
+    case 6: { constexpr int P = 6; __VA_ARGS__; } break;            \
+    case 7: { constexpr int P = 7; __VA_ARGS__; } break;            \
+    case 8: { constexpr int P = 8; __VA_ARGS__; } break;            \
+    default: set_error("p must be in [1,%d], got %d", kMaxP, p); return MI_ERR_INVALID_ARGUMENT; \
+  }
+// the instantiations tuned for narrow rows (the one-pass Hessian in its p <= 4 forms: per-thread P x P matrices in
+// registers, 1024-thread workgroups, the LDS-window forms); p >= 5 takes k_st_hess_wide
+#define DISPATCH_P4(p, ...)                                         \
+  switch (p) {                                                      \
+    case 1: { constexpr int P = 1; __VA_ARGS__; } break;            \
+    case 2: { constexpr int P = 2; __VA_ARGS__; } break;            \
+    case 3: { constexpr int P = 3; __VA_ARGS__; } break;            \
+    case 4: { constexpr int P = 4; __VA_ARGS__; } break;            \
+    default: set_error("internal: narrow-row kernel asked for p = %d", p); return MI_ERR_INTERNAL; \
+  }
+
 // Host-visible progress word written by the device (fine-grained pinned memory).
 struct HostStatus {
   // (B-step launches that did work in the current solve) << 1 | done.  ONE word, written with one store,

@@ -552,37 +552,15 @@ int csr_spmm_launch(const mi_csr *A, int p, const double *V, double *W) {
   const bool no_stream = ctx->cfg.no_spmm_stream;
   if (!no_stream && p >= 1 && p <= kMaxP && sell_stream_ok(A, p)) {
     const int sgrid = (int)std::min<size_t>(ngroups, 256);  // one workgroup per CU, one round
-#define SS(PV, HL, PKV) \
-  hipLaunchKernelGGL((k_spmm_stream<PV, HL, PKV>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, view, V, W)
-#define SSP(PV)                                                 \
-  if (A->halo) { if (A->pk) SS(PV, true, true); else SS(PV, true, false); } \
-  else { if (A->pk) SS(PV, false, true); else SS(PV, false, false); }
-    switch (p) {
-      case 1: SSP(1); break;
-      case 2: SSP(2); break;
-      case 3: SSP(3); break;
-      case 4: SSP(4); break;
-      case 5: SSP(5); break;
-      case 6: SSP(6); break;
-      case 7: SSP(7); break;
-      default: SSP(8); break;
-    }
-#undef SSP
+#define SS(HL, PKV) \
+  DISPATCH_P(p, hipLaunchKernelGGL((k_spmm_stream<P, HL, PKV>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, view, V, W))
+    if (A->halo) { if (A->pk) { SS(true, true); } else { SS(true, false); } }
+    else { if (A->pk) { SS(false, true); } else { SS(false, false); } }
 #undef SS
     MI_HIP(hipGetLastError());
     return MI_OK;
   }
-  switch (p) {
-    case 1: hipLaunchKernelGGL(k_spmm<1>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W); break;
-    case 2: hipLaunchKernelGGL(k_spmm<2>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W); break;
-    case 3: hipLaunchKernelGGL(k_spmm<3>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W); break;
-    case 4: hipLaunchKernelGGL(k_spmm<4>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W); break;
-    case 5: hipLaunchKernelGGL(k_spmm<5>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W); break;
-    case 6: hipLaunchKernelGGL(k_spmm<6>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W); break;
-    case 7: hipLaunchKernelGGL(k_spmm<7>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W); break;
-    case 8: hipLaunchKernelGGL(k_spmm<8>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W); break;
-    default: set_error("p must be in [1,%d], got %d", kMaxP, p); return MI_ERR_INVALID_ARGUMENT;
-  }
+  DISPATCH_P(p, hipLaunchKernelGGL(k_spmm<P>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, V, W));
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
@@ -599,23 +577,11 @@ int csr_spmm_dots(const mi_csr *A, int p, const mi_vec *V, mi_vec *W, int *npart
   if (!ctx->uniform_grid && grid > 256) grid = 256;
   SellView view = sell_view(A);
   KScope ks(ctx, MI_K_SPMM);
-#define SD(PV, HL, PKV)                                                                                       \
-  hipLaunchKernelGGL((k_spmm_dots_stream<PV, HL, PKV>), dim3(grid), dim3(kBlock), 0, ctx->stream, view,       \
-                     (const CgState *)ctx->cg_live, (const double *)V->d, W->d, ctx->partials)
-#define SDP(PV)                                                                     \
-  if (A->halo) { if (A->pk) SD(PV, true, true); else SD(PV, true, false); }         \
-  else { if (A->pk) SD(PV, false, true); else SD(PV, false, false); }
-  switch (p) {
-    case 1: SDP(1); break;
-    case 2: SDP(2); break;
-    case 3: SDP(3); break;
-    case 4: SDP(4); break;
-    case 5: SDP(5); break;
-    case 6: SDP(6); break;
-    case 7: SDP(7); break;
-    default: SDP(8); break;
-  }
-#undef SDP
+#define SD(HL, PKV)                                                                                           \
+  DISPATCH_P(p, hipLaunchKernelGGL((k_spmm_dots_stream<P, HL, PKV>), dim3(grid), dim3(kBlock), 0, ctx->stream, view, \
+                                   (const CgState *)ctx->cg_live, (const double *)V->d, W->d, ctx->partials))
+  if (A->halo) { if (A->pk) { SD(true, true); } else { SD(true, false); } }
+  else { if (A->pk) { SD(false, true); } else { SD(false, false); } }
 #undef SD
   *nparts = grid;
   MI_HIP(hipGetLastError());

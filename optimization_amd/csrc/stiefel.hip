@@ -1170,30 +1170,7 @@ __global__ __launch_bounds__(StBlk<P>::threads) void k_st_polar(size_t n, double
   }
 }
 
-// ---- launch helpers (dispatch on p) --------------------------------------------------------
-#define DISPATCH_P(p, ...)                                          \
-  switch (p) {                                                      \
-    case 1: { constexpr int P = 1; __VA_ARGS__; } break;            \
-    case 2: { constexpr int P = 2; __VA_ARGS__; } break;            \
-    case 3: { constexpr int P = 3; __VA_ARGS__; } break;            \
-    case 4: { constexpr int P = 4; __VA_ARGS__; } break;            \
-    case 5: { constexpr int P = 5; __VA_ARGS__; } break;            \
-    case 6: { constexpr int P = 6; __VA_ARGS__; } break;            \
-    case 7: { constexpr int P = 7; __VA_ARGS__; } break;            \
-    case 8: { constexpr int P = 8; __VA_ARGS__; } break;            \
-    default: set_error("p must be in [1,%d], got %d", kMaxP, p); return MI_ERR_INVALID_ARGUMENT; \
-  }
-// the instantiations tuned for narrow rows (the one-pass Hessian in its p <= 4 forms: per-thread P x P matrices in
-// registers, 1024-thread workgroups, the LDS-window forms); p >= 5 takes k_st_hess_wide
-#define DISPATCH_P4(p, ...)                                         \
-  switch (p) {                                                      \
-    case 1: { constexpr int P = 1; __VA_ARGS__; } break;            \
-    case 2: { constexpr int P = 2; __VA_ARGS__; } break;            \
-    case 3: { constexpr int P = 3; __VA_ARGS__; } break;            \
-    case 4: { constexpr int P = 4; __VA_ARGS__; } break;            \
-    default: set_error("internal: narrow-row kernel asked for p = %d", p); return MI_ERR_INTERNAL; \
-  }
-
+// ---- launch helpers (dispatch on p: DISPATCH_P, DISPATCH_P4 of mi_internal.h) ---------------
 inline int row_grid(const mi_ctx *ctx, size_t n) { return grid_for(ctx, n, 2); }
 // rows wider than 4 doubles run 256-thread workgroups (StBlk): up to kMaxRows of them (one partial row each)
 inline int row_grid(const mi_ctx *ctx, size_t n, int p) {

@@ -1077,25 +1077,441 @@ static unsigned long long result_to_host(mi_ctx *ctx, const CgState *st_final, c
   return seq;
 }
 
-int mi_stpcg_collect(mi_ctx *ctx, mi_stpcg_result *result) {
-  MI_REQUIRE(ctx && result, "null argument");
-  MI_REQUIRE(ctx->cg_deferred, "mi_stpcg_collect: no deferred solve is pending on this context");
-  ctx->cg_deferred = false;
-  if (ctx->cg_deferred_seq) {
-    const unsigned long long seq = ctx->cg_deferred_seq;
-    ctx->cg_deferred_seq = 0;
-    if (__atomic_load_n(ctx->poll_flag, __ATOMIC_ACQUIRE) < seq) {
-      ctx->host_syncs++;
-      MI_TRY(poll_finish(ctx, seq, "stpcg deferred read-back"));
-    }
-  } else {
-    hipError_t e = hipEventQuery(ctx->cg_deferred_ev);
-    if (e == hipErrorNotReady) {
-      e = hipEventSynchronize(ctx->cg_deferred_ev);
-      ctx->host_syncs++;
-    }
-    if (e != hipSuccess) return hip_fail(e, "stpcg deferred read-back", __FILE__, __LINE__);
+}  // extern "C"
+
+// ---- host driver of the fused solve: a plan (what to launch), an owner of the work vectors, a function per step ----
+namespace {
+
+// Dispatch on the compile-time parameters of the solve's kernels, in the shape of DISPATCH_P (mi_internal.h): the
+// statement runs with NAME as a compile-time constant, one of four values (the last one: every other x)
+#define DISPATCH_4(x, NAME, A, B, C, D, ...)                \
+  switch (x) {                                              \
+    case A: { constexpr int NAME = A; __VA_ARGS__; } break; \
+    case B: { constexpr int NAME = B; __VA_ARGS__; } break; \
+    case C: { constexpr int NAME = C; __VA_ARGS__; } break; \
+    default: { constexpr int NAME = D; __VA_ARGS__; } break; \
   }
+#define DISPATCH_PRE(pre, ...) DISPATCH_4(pre, PRE, PRE_NONE, PRE_DIAG, PRE_BLOCK3, PRE_EXTERNAL, __VA_ARGS__)
+// components of the operator's partial rows in the recurrence form (dir_comps), p = 1 ... 4
+#define DISPATCH_KC(kc, ...) DISPATCH_4(kc, KC, 4, 6, 9, 16, __VA_ARGS__)
+// p = 5 ... 8: 18, 24, 31, 39 components (3 + p (p + 1) / 2).  Never folded (the host keeps the separate exchange for
+// them), and launched from the uncapped kernel: 39 reduced values per thread do not fit the 64 vector registers the
+// two-workgroups-per-CU twins are held to
+#define DISPATCH_KC_WIDE(kc, ...) DISPATCH_4(kc, KC, 18, 24, 31, 39, __VA_ARGS__)
+// row width of the direction kernel (0: flat form)
+#define DISPATCH_SP(sp, ...) \
+  if ((sp) == 0) { constexpr int SP = 0; __VA_ARGS__; } else DISPATCH_4(sp, SP, 1, 2, 3, 4, __VA_ARGS__)
+
+// Which inclusion of stpcg_kernels.inc a single-rank launch takes (`if constexpr`: only the chosen kernel is
+// instantiated).  Recurrence form, 4 / 6 / 9 components: k_cg_update (SIGMA) or k_cg_update_ns; 16 components always need
+// the 80-SGPR twin (see above).
+template <bool SIGMA, int KC>
+auto cg_update_recur_kernel() {
+  if constexpr (SIGMA && KC == 16) return &k_cg_update_s80<PRE_NONE, false, KC, NoFold>;
+  else if constexpr (SIGMA) return &k_cg_update<PRE_NONE, false, KC, NoFold>;
+  else if constexpr (KC == 16) return &k_cg_update_ns_s80<PRE_NONE, false, KC, NoFold>;
+  else return &k_cg_update_ns<PRE_NONE, false, KC, NoFold>;
+}
+// (rows of 0 / 1 doubles are the two forms that count on 8 waves per SIMD -- the twin wherever the plain kernel is
+// allocated more than 80 scalar registers: rows of 1, and the slot-reading flat form; wider rows are bound by their
+// vector registers)
+template <bool FS, int SP>
+auto cg_pupdate_kernel() {
+  if constexpr (SP == 1 || (FS && SP == 0)) return &k_cg_pupdate_s80<FS, SP, NoFold>;
+  else return &k_cg_pupdate<FS, SP, NoFold>;
+}
+
+// What one solve launches.  Filled ONCE by stpcg_plan, before anything is allocated or enqueued, and const from there on:
+// every enqueue step reads its decisions here and takes none of its own.  (Each field's rule: stpcg_plan.)
+struct StpcgPlan {
+  size_t n;
+  bool observed, sharded, rows, lockstep, recur, folded, init_fused, gdir_in_scalar_init;
+  bool twok, early, defer;  // forms of the step, mutually exclusive (none of them: the plain three-kernel step)
+  int pre, run_ahead, grid, gns, sp, kc, reanchor;
+  const mi_dirgram *dgp;
+  CgConst cc;
+};
+
+int stpcg_plan(const mi_ctx *ctx, const mi_op *H, const mi_precon *P, const mi_stpcg_params *prm, size_t n,
+               bool observed, StpcgPlan &pl) {
+  pl.n = n;
+  pl.observed = observed;
+  pl.pre = !P ? PRE_NONE : (P->kind == 1 ? PRE_DIAG : (P->kind == 2 ? PRE_BLOCK3 : PRE_EXTERNAL));
+  MI_REQUIRE(pl.pre != PRE_BLOCK3 || n % 3 == 0, "block-Jacobi preconditioner needs n divisible by 3");
+  // several ranks: the partial rows themselves are all-reduced (rows_mode) and the consumers keep
+  // their prologue re-reduction; the slot variants stay reachable through MI355OPT_FORCE_SLOT_PATH
+  pl.sharded = slot_mode(ctx);
+  pl.rows = rows_mode(ctx);
+  // direction-Gram fusion (mi_op::dirgram): one-pass Hessian, the Gram rows come from the direction kernel
+  pl.dgp = (!ctx->no_dirgram && H->dirgram && H->apply_dir) ? H->dirgram : nullptr;
+  // rows wider than 4 doubles (Stiefel p = 5 ... 8) have the one-pass operator in its recurrence form only (no
+  // preconditioner); with one, the operator keeps its two passes and the direction kernel its flat form
+  if (pl.dgp && pl.dgp->p > 4 && (pl.pre != PRE_NONE || ctx->dirgram_direct)) pl.dgp = nullptr;
+  MI_REQUIRE(!pl.dgp || (pl.dgp->p >= 1 && pl.dgp->p <= kMaxP && pl.dgp->n * (size_t)pl.dgp->p == n),
+             "operator's direction-Gram description does not match the problem dimension");
+  // (default depth 3: depth 2 gives the same cfg2 step and -0.6 % on a cfg3 TNT run, DESIGN 3.3)
+  pl.run_ahead = prm->run_ahead > 0 ? prm->run_ahead : 3;
+  pl.lockstep = (ctx->comm != nullptr && ctx->world_size > 1) || ctx->force_lockstep;
+  pl.grid = (pl.pre == PRE_BLOCK3) ? grid_for(ctx, n / 3, 2) : grid_for(ctx, n, 4);
+  pl.cc = CgConst{prm->Delta, prm->Delta * prm->Delta, prm->epsilon, (unsigned long long)prm->max_iterations, 0ull, 0ull};
+  const size_t n2 = n >> 1, step = (size_t)pl.grid * kBlock;
+  pl.cc.rag0 = (n2 / step) * step;
+  pl.cc.rag_per = (n2 - pl.cc.rag0 + (size_t)pl.grid - 1) / (size_t)pl.grid;
+  // recurrence form of the direction Gram: needs v == r (no preconditioner)
+  pl.recur = pl.dgp && pl.pre == PRE_NONE && !ctx->dirgram_direct;
+  pl.gns = pl.dgp ? pl.dgp->p * (pl.dgp->p + 1) / 2 : 0;
+  pl.sp = (pl.dgp && !pl.recur) ? pl.dgp->p : 0;  // row form of k_cg_pupdate only in the direct form
+  pl.kc = pl.recur ? dir_comps(pl.dgp->p) : 3;    // components of the operator's partial rows
+  // Several ranks through the peer-memory layer, unpreconditioned recurrence form (the cfg2 / cfg4 hot loop): the two
+  // scalar exchanges of an iteration are folded into the prologues of their consumers (no exchange kernels).  Every
+  // other combination keeps the separate exchange kernels.
+  // (the folded exchange carries at most kIpcVals = 16 values: p <= 4)
+  pl.folded = pl.sharded && pl.recur && pl.kc <= kIpcVals && comm_fold_enabled(ctx) && !ctx->force_slot_path;
+  // unpreconditioned recurrence form: initialisation and the first direction's Gram rows in one pass
+  // (k_cg_init_dirgram); one rank, nothing to exchange: G(p0), G(r0) set by k_cg_scalar_init itself
+  pl.init_fused = pl.recur && n == pl.dgp->n * (size_t)pl.dgp->p;
+  pl.gdir_in_scalar_init = pl.recur && !pl.sharded && !pl.rows;
+  // opt-in experiment: the two-kernel step (k_cg_step2; one rank, Stiefel(n,3) in the window form)
+  // (an observed solve keeps the plain three-kernel step: the two-kernel step has no point between the operator and
+  // the update, the early-s form is an experiment, and the deferred-s form would show the observer of an odd pass an s
+  // that is one term short)
+  pl.twok = ctx->cfg.two_kernel_step && pl.recur && pl.dgp->twok && pl.dgp->p == 3 && !pl.sharded && !pl.rows &&
+            !pl.lockstep && pl.init_fused && pl.gdir_in_scalar_init && !observed;
+  // (the early-s form: single context, v = r or any plain vector, at most three elements per thread, <= 512 rows)
+  pl.early = !pl.sharded && !pl.rows && pl.sp == 0 && ctx->cfg.early_s && pl.grid <= 512 &&
+             pl.cc.rag0 <= 2ull * (size_t)pl.grid * kBlock && (n >> 1) < ((size_t)1 << 31) && !observed;
+  // deferred-s form (k_cg_pupdate_ds): single context, flat direction kernel; the direction lives in two buffers that
+  // swap every iteration -- StpcgBufs::p is the current one wherever a step names it
+  pl.defer = !pl.sharded && !pl.rows && !pl.lockstep && !pl.twok && pl.sp == 0 && !pl.early && ctx->cfg.defer_s &&
+             !observed;
+  // r06: re-anchor the recurrence form's G(p), G(r) by the direct form every `reanchor` iterations, 0: never (the count is
+  // the loop index: the same on every rank, so the exchanges it carries stay matched across ranks)
+  pl.reanchor = (pl.recur && !pl.twok && ctx->cfg.reanchor > 0) ? ctx->cfg.reanchor : 0;
+  return MI_OK;
+}
+
+// What the enqueue steps work on: the solve's work vectors (pool vectors), which it owns, and the buffers that are fixed
+// for the solve.  Its destructor is the ONE way out of a solve once it exists: a `return` anywhere behind it can neither
+// leak the vectors nor leave the context marked as inside a solve.  Only p / p2 change inside the loop (the deferred-s
+// form's swap, stpcg_bstep): every step reads them here, so the swap reaches all later ones.
+struct StpcgBufs {
+  mi_ctx *ctx;
+  mi_vec *r = nullptr, *v = nullptr, *p = nullptr, *p2 = nullptr, *Hp = nullptr;
+  bool ok = false;  // set on the successful exit only
+  const mi_vec *g = nullptr; mi_vec *s_out = nullptr; mi_op *H = nullptr;
+  mi_precon *P = nullptr; const mi_stpcg_params *prm = nullptr;
+  double *vd = nullptr;          // v aliases r when P is absent (:231,383)
+  const double *pred = nullptr;  // data of the built-in preconditioners
+  DirGramArgs dga{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  double *slots_g = nullptr, *slots_a = nullptr, *slots_b = nullptr;  // (slots_g: the recurrence form's, kc <= 16 doubles)
+  CgState *st0 = nullptr, *st1 = nullptr;
+  double *tr = nullptr;          // device trace (4 rows of tcap doubles), or null
+  size_t tcap = 0;
+  // r'-halo form (Config::halo_rprime): the halo rows of r' travel with the <r,v> all-reduce, halo(p') is formed locally
+  bool rprime = false;
+  unsigned long long *peek_dev = nullptr;  // observed solve: device address of the pinned words
+  explicit StpcgBufs(mi_ctx *c) : ctx(c) {}
+  StpcgBufs(const StpcgBufs &) = delete;
+  StpcgBufs &operator=(const StpcgBufs &) = delete;
+  ~StpcgBufs() {
+    ctx->cg_live = nullptr;
+    // a folded halo push nobody consumed must not outlive the solve on ANY exit: p is a recycled pool pointer, and the
+    // next solve's first Hessian pass would match the stale (A, p, V) entry, skip the real exchange and wait for a flag
+    // that never comes (r04, ADVICE: an error exit between comm_halo_fold_next and the pass used to leave it set)
+    comm_halo_fold_drop(ctx);
+    // (an error exit: what was enqueued may still be reading the vectors that go back to the pool)
+    if (!ok) (void)hipStreamSynchronize(ctx->stream);
+    for (mi_vec *x : {r, p, p2, Hp, v}) mi_vec_destroy(x);  // (null: nothing to do)
+  }
+};
+
+int stpcg_bufs(mi_ctx *ctx, const StpcgPlan &pl, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpcg_params *prm,
+               mi_vec *s_out, const mi_stpcg_trace *trace, StpcgBufs &b) {
+  const size_t n = pl.n;
+  b.g = g, b.s_out = s_out, b.H = H, b.P = P, b.prm = prm;
+  MI_TRY(mi_vec_create(ctx, n, &b.r));
+  MI_TRY(mi_vec_create(ctx, n, &b.p));
+  MI_TRY(mi_vec_create(ctx, n, &b.Hp));
+  if (pl.pre != PRE_NONE) MI_TRY(mi_vec_create(ctx, n, &b.v));
+  if (pl.defer) MI_TRY(mi_vec_create(ctx, n, &b.p2));
+  b.vd = (pl.pre == PRE_NONE) ? b.r->d : b.v->d;
+  b.pred = P ? P->data : nullptr;
+  if (trace && trace->cap) {
+    if (ctx->trace_cap < trace->cap) {
+      if (ctx->trace_dev) MI_HIP(hipFree(ctx->trace_dev));
+      MI_HIP(hipMalloc((void **)&ctx->trace_dev, 4 * trace->cap * sizeof(double)));
+      ctx->trace_cap = trace->cap;
+    }
+    b.tcap = ctx->trace_cap;  // layout stride
+    b.tr = ctx->trace_dev;
+  }
+  if (pl.dgp)
+    b.dga = DirGramArgs{pl.dgp->X, pl.dgp->Y, pl.dgp->S, ctx->partials2, pl.recur ? ctx->scalars + SLOT_GDIR : nullptr,
+                        pl.gns};
+  b.slots_g = ctx->scalars + SLOT_GRAM, b.slots_a = ctx->scalars + SLOT_CG, b.slots_b = ctx->scalars + SLOT_CG + 4;
+  b.st0 = ctx->cg, b.st1 = ctx->cg1;
+  // observed solve: k_cg_peek's four words land at the head of the pinned state copy (free until the final read-back)
+  if (pl.observed) {
+    const hipError_t e = hipHostGetDevicePointer((void **)&b.peek_dev, ctx->cg_host, 0);
+    if (e != hipSuccess) return hip_fail(e, "stpcg observer: device address of the pinned words", __FILE__, __LINE__);
+  }
+  return MI_OK;
+}
+
+// completes the sum of k components of `count` partial rows across the ranks (one rank: nothing to do)
+int stpcg_allreduce(mi_ctx *ctx, const StpcgPlan &pl, double *partials, int count, int k, double *slots) {
+  return pl.sharded ? reduce_rows_allreduce(ctx, partials, count, k, slots)
+                    : pl.rows ? comm_allreduce_rows(ctx, partials, k) : MI_OK;
+}
+
+// ---- the argument list of each kernel family, once ----
+int launch_dirgram(mi_ctx *ctx, const StpcgPlan &pl, const StpcgBufs &b, const double *vec) {
+  DISPATCH_P(pl.dgp->p, hipLaunchKernelGGL(k_cg_dirgram<P>, dim3(pl.grid), dim3(StBlk<P>::threads), 0, ctx->stream,
+                                           pl.dgp->n, vec, b.dga));
+  return MI_OK;
+}
+void launch_gdir_anchor(mi_ctx *ctx, const StpcgPlan &pl, const StpcgBufs &b, double *dst, double *dst2) {
+  hipLaunchKernelGGL(k_cg_gdir_anchor, dim3(1), dim3(kBlock), 0, ctx->stream, (const double *)ctx->partials2, pl.grid,
+                     pl.gns, (const double *)b.slots_g, pl.sharded ? 1 : 0, (const CgState *)b.st0, dst, dst2);
+}
+template <class K, class FOLD>
+void launch_cg_update(K kernel, mi_ctx *ctx, const StpcgPlan &pl, const StpcgBufs &b, int nparts, const FOLD &fold) {
+  hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(kBlock), 0, ctx->stream, pl.n, pl.cc, (const CgState *)b.st0, b.st1,
+                     (const double *)ctx->partials, nparts, (const double *)(pl.recur ? b.slots_g : b.slots_a),
+                     (const double *)b.p->d, (const double *)b.Hp->d, b.pred, b.s_out->d, b.r->d, b.vd, ctx->partials_b,
+                     b.dga, fold);
+}
+template <class K, class FOLD>
+void launch_cg_pupdate(K kernel, mi_ctx *ctx, const StpcgPlan &pl, const StpcgBufs &b, const FOLD &fold) {
+  hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(kBlock), 0, ctx->stream, pl.n, pl.cc, (const CgState *)b.st1, b.st0,
+                     (const double *)ctx->partials_b, pl.grid, (const double *)b.slots_b, (const double *)b.vd, b.p->d,
+                     b.s_out->d, ctx->status_dev, b.tr, b.tcap, b.dga, fold);
+}
+
+// ---- enqueue steps ----------------------------------------------------------------------------
+// v = P(r) by the preconditioner's own kernels, then the partial rows of <r,v> (`first`: in the set-up, and p = -v)
+int stpcg_precondition(mi_ctx *ctx, const StpcgPlan &pl, StpcgBufs &b, bool first) {
+  mi_precon *P = b.P;
+  if (P->apply_project) MI_TRY(P->apply_project(P, b.r, b.v, b.prm->constraint_At));  // (v, lambda) = P(r); r -= A' lambda (:386,403)
+  else MI_TRY(P->apply(P, b.r, b.v));                                                 // v = P(r) (:386)
+  hipLaunchKernelGGL(first ? &k_cg_dot_rv<true> : &k_cg_dot_rv<false>, dim3(pl.grid), dim3(kBlock), 0, ctx->stream, pl.n,
+                     (const CgState *)(first ? b.st0 : b.st1), (const double *)b.r->d, (const double *)b.v->d, b.p->d,
+                     ctx->partials_b);
+  return MI_OK;
+}
+
+// set-up: initialisation, the first direction's Gram rows, scalar init
+int stpcg_setup(mi_ctx *ctx, const StpcgPlan &pl, StpcgBufs &b) {
+  hipStream_t st = ctx->stream;
+  const int grid = pl.grid;
+  {
+    KScope ks(ctx, MI_K_CG_INIT);
+    if (pl.init_fused) {
+      DISPATCH_P(pl.dgp->p, hipLaunchKernelGGL(k_cg_init_dirgram<P>, dim3(grid), dim3(StBlk<P>::threads), 0, st, pl.dgp->n,
+                                               (const double *)b.g->d, b.r->d, b.p->d, b.s_out->d, ctx->partials_b, b.dga));
+    } else {
+      DISPATCH_PRE(pl.pre, hipLaunchKernelGGL(k_cg_init<PRE>, dim3(grid), dim3(kBlock), 0, st, pl.n, (const double *)b.g->d,
+                                              b.pred, b.r->d, b.vd, b.p->d, b.s_out->d, ctx->partials_b));
+    }
+  }
+  if (pl.pre == PRE_EXTERNAL) MI_TRY(stpcg_precondition(ctx, pl, b, true));
+  if (pl.dgp) {
+    if (!pl.init_fused) MI_TRY(launch_dirgram(ctx, pl, b, b.p->d));
+    if (pl.recur && !pl.gdir_in_scalar_init) {
+      MI_TRY(stpcg_allreduce(ctx, pl, ctx->partials2, grid, pl.gns, b.slots_g));
+      hipLaunchKernelGGL(k_cg_gdir_init, dim3(1), dim3(kBlock), 0, st, (const double *)ctx->partials2, grid, pl.gns,
+                         (const double *)b.slots_g, pl.sharded ? 1 : 0, b.dga.gdir);
+    }
+  }
+  const CgSetup cfg{b.prm->Delta, b.prm->kappa_fgr, b.prm->theta, b.prm->epsilon,
+                    (unsigned long long)b.prm->max_iterations};
+  MI_TRY(stpcg_allreduce(ctx, pl, ctx->partials_b, grid, 1, b.slots_b));
+  if (pl.sharded)
+    hipLaunchKernelGGL(k_cg_scalar_init<true>, dim3(1), dim3(kBlock), 0, st, b.st0, cfg, (const double *)ctx->partials_b,
+                       grid, (const double *)b.slots_b, ctx->status_dev, (const double *)nullptr, 0, 0, (double *)nullptr);
+  else
+    hipLaunchKernelGGL(k_cg_scalar_init<false>, dim3(1), dim3(kBlock), 0, st, b.st0, cfg, (const double *)ctx->partials_b,
+                       grid, (const double *)b.slots_b, ctx->status_dev, (const double *)ctx->partials2, grid, pl.gns,
+                       pl.gdir_in_scalar_init ? b.dga.gdir : (double *)nullptr);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "stpcg init launch", __FILE__, __LINE__);
+  return MI_OK;
+}
+
+// re-anchor (StpcgPlan::reanchor): G(p), G(r) of the recurrence form, formed afresh by the direct form
+int stpcg_reanchor(mi_ctx *ctx, const StpcgPlan &pl, StpcgBufs &b) {
+  const int grid = pl.grid, gns = pl.gns;
+  if (pl.dgp->p <= 4) {
+    // rows of <= 4 doubles: both Grams from ONE pass over X, Y, p, r and one (all-)reduction of 2 gns components
+    DISPATCH_P4(pl.dgp->p, hipLaunchKernelGGL(k_cg_dirgram2<P>, dim3(grid), dim3(kBlock), 0, ctx->stream, pl.dgp->n,
+                                              (const CgState *)b.st0, (const double *)b.p->d, (const double *)b.r->d, b.dga));
+    MI_TRY(stpcg_allreduce(ctx, pl, ctx->partials2, grid, 2 * gns, b.slots_g));
+    launch_gdir_anchor(ctx, pl, b, b.dga.gdir + SLOT_GDIR_P, b.dga.gdir);
+  } else {
+    for (int which = 0; which < 2; ++which) {
+      MI_TRY(launch_dirgram(ctx, pl, b, which == 0 ? b.p->d : b.r->d));
+      MI_TRY(stpcg_allreduce(ctx, pl, ctx->partials2, grid, gns, b.slots_g));
+      launch_gdir_anchor(ctx, pl, b, b.dga.gdir + (which == 0 ? SLOT_GDIR_P : 0), nullptr);
+    }
+  }
+  return MI_OK;
+}
+
+// operator pass: Hp = H(p) (:294) + partial rows of <p,Hp>, <Hp,Hp>, <p,p> in ctx->partials
+int stpcg_operator(mi_ctx *ctx, const StpcgPlan &pl, StpcgBufs &b, int *nparts) {
+  if (pl.dgp) return b.H->apply_dir(b.H, b.p, b.Hp, pl.recur ? -1 : pl.grid, nparts);
+  if (b.H->apply_dots) return b.H->apply_dots(b.H, b.p, b.Hp, nparts);
+  MI_TRY(b.H->apply(b.H, b.p, b.Hp));
+  return launch_dot3_partials(ctx, pl.n, b.p->d, b.Hp->d, nparts);
+}
+
+// the whole iteration of the two-kernel step (StpcgPlan::twok): two launches; the state ping-pongs between st0 and st1
+// ACROSS iterations, *st_final is the copy this one wrote
+int stpcg_step2(mi_ctx *ctx, const StpcgPlan &pl, StpcgBufs &b, size_t k, CgState **st_final) {
+  CgState *cur = (k & 1) ? b.st1 : b.st0, *nxt = (k & 1) ? b.st0 : b.st1;
+  int nparts = 0;
+  ctx->cg_live = cur;
+  ctx->twok_r = b.r->d;
+  const int st_op = b.H->apply_dir(b.H, b.p, b.Hp, -2, &nparts);
+  ctx->twok_r = nullptr;
+  MI_TRY(st_op);
+  KScope ks(ctx, MI_K_CG_UPDATE);
+  hipLaunchKernelGGL(k_cg_step2<6>, dim3(pl.grid), dim3(kBlock), 0, ctx->stream, pl.n, pl.cc, (const CgState *)cur, nxt,
+                     (const double *)ctx->partials, nparts, (const double *)b.Hp->d, b.r->d, b.p->d, b.s_out->d,
+                     ctx->status_dev, b.tr, b.tcap, b.dga);
+  *st_final = nxt;
+  return MI_OK;
+}
+
+// Observed solve, between the operator pass and the A-step: alpha_k and the decisions of :300-362 to the host (one small
+// kernel and one polled wait per pass), then the user's function.
+// *says: go on; enqueue nothing more; or enqueue the rest of this pass, which ends the solve (no further peek)
+enum ObserverSays { OBS_GO_ON, OBS_STOP, OBS_LAST_PASS };
+int stpcg_observe(mi_ctx *ctx, const StpcgPlan &pl, StpcgBufs &b, mi_stpcg_observer observer, void *observer_user,
+                  int nparts, ObserverSays *says) {
+  hipStream_t st = ctx->stream;
+  ctx->host_syncs++;
+  unsigned long long *flag = nullptr;
+  const unsigned long long seq = poll_begin(ctx, &flag);
+  {
+    KScope ks(ctx, MI_K_CG_SCALAR_A);
+    hipLaunchKernelGGL(k_cg_peek, dim3(1), dim3(kBlock), 0, st, pl.cc, (const CgState *)b.st0,
+                       (const double *)ctx->partials, nparts, b.peek_dev, seq ? flag : (unsigned long long *)nullptr, seq);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "stpcg observer peek launch", __FILE__, __LINE__);
+  MI_TRY(poll_finish(ctx, seq, "stpcg observer peek"));
+  const volatile unsigned long long *pk = reinterpret_cast<const volatile unsigned long long *>(ctx->cg_host);
+  const int mode_in = (int)pk[0], mode_a = (int)pk[1];
+  *says = OBS_STOP;
+  // (this pass's operator is already enqueued -- hvp_calls counts ENQUEUED passes, here as in the un-observed solve --
+  // unless the test of the status word at the top of the loop happened to see the exit first)
+  if (mode_in == CG_DONE) return MI_OK;  // the last pass's B-step (or the initialisation) ended the solve: :285, :290
+  if (mode_a != CG_RUN) {
+    *says = OBS_LAST_PASS;  // kernel-of-H or boundary exit inside this pass: the reference does not call either
+    return MI_OK;
+  }
+  double alpha_k;
+  const unsigned long long abits = pk[2];
+  memcpy(&alpha_k, &abits, sizeof(alpha_k));
+  ctx->cg_in_observer = true;
+  const int stop = observer(observer_user, (size_t)pk[3], b.s_out, b.r, b.v ? b.v : b.r, b.p, alpha_k);
+  ctx->cg_in_observer = false;
+  *says = stop ? OBS_STOP : OBS_GO_ON;
+  if (!stop) return MI_OK;
+  hipLaunchKernelGGL(k_cg_user_stop, dim3(1), dim3(64), 0, st, b.st0, ctx->status_dev);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "stpcg observer stop launch", __FILE__, __LINE__);
+  return MI_OK;
+}
+
+// A-step (k_cg_update*): the operator's partial rows complete across the ranks, then the update
+int stpcg_astep(mi_ctx *ctx, const StpcgPlan &pl, StpcgBufs &b, size_t k, int nparts) {
+  // (deferred-s form, odd k: a term of s is pending, and a boundary step is the direction kernel's to apply behind it)
+  const bool sigma_later = pl.defer && (k & 1);
+  // recurrence form: 3 dots + the Gram rows of Hp in one reduction (and one exchange across ranks)
+  FoldArgs fold_a;
+  // folded: the sum over the ranks completes in the kernel's own prologue (comm_ipc.h): no exchange kernel
+  if (pl.folded) fold_a = comm_fold_next(ctx);
+  else MI_TRY(stpcg_allreduce(ctx, pl, ctx->partials, nparts, pl.kc, pl.recur ? b.slots_g : b.slots_a));
+  KScope ks(ctx, MI_K_CG_UPDATE);
+  // (every kernel named here is launched by some form of the solve: the choice inside a dispatch adds no instantiation)
+  if (!pl.recur) {
+    DISPATCH_PRE(pl.pre, launch_cg_update(pl.sharded    ? &k_cg_update<PRE, true, 3, NoFold>
+                                          : sigma_later ? &k_cg_update_ns<PRE, false, 3, NoFold>
+                                                        : &k_cg_update<PRE, false, 3, NoFold>,
+                                          ctx, pl, b, nparts, NoFold{}));
+  } else if (pl.kc > 16) {
+    DISPATCH_KC_WIDE(pl.kc, launch_cg_update(pl.sharded    ? &k_cg_update<PRE_NONE, true, KC, NoFold>
+                                             : sigma_later ? &k_cg_update_ns<PRE_NONE, false, KC, NoFold>
+                                                           : &k_cg_update<PRE_NONE, false, KC, NoFold>,
+                                             ctx, pl, b, nparts, NoFold{}));
+  } else if (pl.folded) {
+    DISPATCH_KC(pl.kc, launch_cg_update(&k_cg_update_s80<PRE_NONE, false, KC, FoldArgs>, ctx, pl, b, nparts, fold_a));
+  } else {
+    DISPATCH_KC(pl.kc, launch_cg_update(pl.sharded    ? &k_cg_update_s80<PRE_NONE, true, KC, NoFold>
+                                        : sigma_later ? cg_update_recur_kernel<false, KC>()
+                                                      : cg_update_recur_kernel<true, KC>(),
+                                        ctx, pl, b, nparts, NoFold{}));
+  }
+  return MI_OK;
+}
+
+// B-step (k_cg_pupdate*): the partial rows of <r,v> complete across the ranks, then the new direction (with the r'-halo
+// tail).  The deferred-s form swaps p and p2 here.
+int stpcg_bstep(mi_ctx *ctx, const StpcgPlan &pl, StpcgBufs &b, size_t k) {
+  hipStream_t st = ctx->stream;
+  const mi_dirgram *dgp = pl.dgp;
+  const int grid = pl.grid;
+  if (pl.folded) {
+    const FoldArgs fold_b = comm_fold_next(ctx);  // (folded <=> recurrence form <=> sp == 0)
+    // ... and the halo exchange of the NEXT Hessian pass rides in this kernel's stores of the new direction
+    FoldPush fp{fold_b, HaloPush{}};
+    const bool push = dgp->halo_A && k + 1 < b.prm->max_iterations &&
+                      comm_halo_fold_next(ctx, dgp->halo_A, dgp->p, b.p->d, &fp.h);
+    KScope ks(ctx, MI_K_CG_PUPDATE);
+    if (push) launch_cg_pupdate(&k_cg_pupdate_s80<false, 0, FoldPush>, ctx, pl, b, fp);
+    else launch_cg_pupdate(&k_cg_pupdate_s80<false, 0, FoldArgs>, ctx, pl, b, fold_b);
+  } else if (pl.sharded) {
+    MI_TRY(reduce_rows_allreduce(ctx, ctx->partials_b, grid, 1, b.slots_b));
+    if (b.rprime) MI_TRY(comm_rprime_exchange(ctx, dgp->halo_A, dgp->p, b.r->d, nullptr, 0));
+    KScope ks(ctx, MI_K_CG_PUPDATE);
+    DISPATCH_SP(pl.sp, launch_cg_pupdate(cg_pupdate_kernel<true, SP>(), ctx, pl, b, NoFold{}));
+  } else {
+    if (pl.rows && b.rprime) MI_TRY(comm_rprime_exchange(ctx, dgp->halo_A, dgp->p, b.r->d, ctx->partials_b, 1));
+    else if (pl.rows) MI_TRY(comm_allreduce_rows(ctx, ctx->partials_b, 1));
+    KScope ks(ctx, MI_K_CG_PUPDATE);
+    if (pl.early) {
+      hipLaunchKernelGGL(k_cg_pupdate_early, dim3(grid), dim3(kBlock), 0, st, pl.n, pl.cc, (const CgState *)b.st1, b.st0,
+                         (const double *)ctx->partials_b, grid, (const double *)b.vd, b.p->d, b.s_out->d, ctx->status_dev,
+                         b.tr, b.tcap, b.dga);
+    } else if (pl.defer && ((k & 1) || k + 1 < b.prm->max_iterations)) {
+      // odd k: the pending term and this one (FLUSH); even k: this one stays pending
+      hipLaunchKernelGGL((k & 1) ? &k_cg_pupdate_ds<true> : &k_cg_pupdate_ds<false>, dim3(grid), dim3(kBlock), 0, st,
+                         pl.n, pl.cc, (const CgState *)b.st1, b.st0, (const double *)ctx->partials_b, grid,
+                         (const double *)b.vd, (const double *)b.p->d, b.p2->d, b.s_out->d, ctx->status_dev, b.tr,
+                         b.tcap, b.dga);
+      std::swap(b.p, b.p2);
+    } else {  // (deferred-s form: the last enqueued iteration is an even one)
+      DISPATCH_SP(pl.sp, launch_cg_pupdate(cg_pupdate_kernel<false, SP>(), ctx, pl, b, NoFold{}));
+    }
+  }
+  if (b.rprime && (pl.sharded || pl.rows)) {
+    const double *hr = nullptr;
+    double *hp = nullptr;
+    size_t cnt = 0;
+    comm_rprime_buffers(ctx, dgp->halo_A, dgp->p, &hr, &hp, &cnt);
+    if (cnt) {
+      const int hg = (int)std::max<size_t>(1, std::min<size_t>((cnt + 255) / 256, 512));
+      hipLaunchKernelGGL(k_halo_dir, dim3(hg), dim3(256), 0, st, (const CgState *)b.st0, hr, hp, cnt);
+    }
+    comm_rprime_mark(ctx, dgp->halo_A, dgp->p, b.p->d);
+  }
+  return MI_OK;
+}
+
+// the pinned copy of the final state -> the caller's result (mi_stpcg and mi_stpcg_collect; hvp_calls is theirs)
+int stpcg_result_from_host(mi_ctx *ctx, mi_stpcg_result *result) {
   int ipc_err = 0;
   (void)mi_comm_ipc_error(ctx, &ipc_err);
   if (ipc_err) {
@@ -1107,15 +1523,64 @@ int mi_stpcg_collect(mi_ctx *ctx, mi_stpcg_result *result) {
   result->num_iterations = (size_t)f.k;
   result->exit_reason = f.exit_reason;
   result->rv_final = f.rv;
-  result->hvp_calls = ctx->cg_deferred_hvp;
   return precon_fail_check(ctx, result);
 }
 
-// mi_stpcg (observer == nullptr) and mi_stpcg_observed share this body; every `observed` below is false for the former,
+// read-back of the final state: deferred (the copy travels behind the solve; whoever waits for the stream next, or
+// mi_stpcg_collect, completes it), or here
+int stpcg_readback(mi_ctx *ctx, const StpcgPlan &pl, const StpcgBufs &b, const CgState *st_final, mi_stpcg_trace *trace,
+                   mi_stpcg_result *result) {
+  hipStream_t st = ctx->stream;
+  const mi_precon *P = b.P;
+  const bool tracing = trace && trace->cap;
+  *precon_fail_host(ctx) = 0.0;
+  if (b.prm->defer_result && !tracing && !pl.observed) {
+    hipError_t e = hipSuccess;
+    ctx->cg_deferred_seq = result_to_host(ctx, st_final, P);
+    if (!ctx->cg_deferred_seq) {
+      if (!ctx->cg_deferred_ev) e = hipEventCreateWithFlags(&ctx->cg_deferred_ev, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipMemcpyAsync(ctx->cg_host, st_final, sizeof(CgState), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess && P && P->fail_word)
+        e = hipMemcpyAsync(precon_fail_host(ctx), P->fail_word, sizeof(double), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipEventRecord(ctx->cg_deferred_ev, st);
+    }
+    if (e != hipSuccess) return hip_fail(e, "stpcg deferred read-back", __FILE__, __LINE__);
+    ctx->cg_deferred = true;
+    ctx->cg_deferred_hvp = result->hvp_calls;
+    result->update_step_M_norm = result->rv_final = 0;
+    result->num_iterations = 0, result->exit_reason = -1, result->precon_status = 0;
+    return MI_OK;
+  }
+  ctx->host_syncs++;
+  if (const unsigned long long seq = result_to_host(ctx, st_final, P)) {
+    MI_TRY(poll_finish(ctx, seq, "stpcg read-back"));
+  } else {
+    hipError_t e = hipMemcpyAsync(ctx->cg_host, st_final, sizeof(CgState), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && P && P->fail_word)
+      e = hipMemcpyAsync(precon_fail_host(ctx), P->fail_word, sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "stpcg read-back", __FILE__, __LINE__);
+  }
+  MI_TRY(stpcg_result_from_host(ctx, result));
+  if (tracing) {
+    const size_t len = result->num_iterations < trace->cap ? result->num_iterations : trace->cap;
+    trace->len = len;
+    double *dst[4] = {trace->alpha, trace->beta, trace->kappa, trace->rv};
+    for (int c = 0; c < 4; ++c)
+      if (dst[c] && len) {
+        const hipError_t e = hipMemcpy(dst[c], ctx->trace_dev + (size_t)c * b.tcap, len * sizeof(double),
+                                       hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(e, "stpcg trace copy", __FILE__, __LINE__);
+      }
+  }
+  return MI_OK;
+}
+
+// mi_stpcg (observer == nullptr) and mi_stpcg_observed share this body; the plan's `observed` is false for the former,
 // which enqueues exactly what it always did
-static int stpcg_solve(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpcg_params *prm,
-                       mi_stpcg_observer observer, void *observer_user, mi_vec *s_out, mi_stpcg_result *result,
-                       mi_stpcg_trace *trace) {
+int stpcg_solve(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, const mi_stpcg_params *prm,
+                mi_stpcg_observer observer, void *observer_user, mi_vec *s_out, mi_stpcg_result *result,
+                mi_stpcg_trace *trace) {
   MI_REQUIRE(ctx && g && H && prm && s_out && result, "null argument");
   MI_REQUIRE(g->ctx == ctx && s_out->ctx == ctx && H->ctx == ctx, "objects belong to another context");
   MI_REQUIRE(g->n == s_out->n && g->n == H->n, "dimension mismatch: g %zu, s %zu, H %zu", g->n,
@@ -1150,560 +1615,91 @@ static int stpcg_solve(mi_ctx *ctx, const mi_vec *g, mi_op *H, mi_precon *P, con
              "should be a small positive number in the range (0,1)");
 
   RangeScope range("mi_stpcg");
-  comm_halo_fold_drop(ctx);  // (nothing may be pending from an earlier solve: see cleanup)
-  const size_t n = g->n;
-  const int pre = !P ? PRE_NONE : (P->kind == 1 ? PRE_DIAG : (P->kind == 2 ? PRE_BLOCK3 : PRE_EXTERNAL));
-  MI_REQUIRE(pre != PRE_BLOCK3 || n % 3 == 0, "block-Jacobi preconditioner needs n divisible by 3");
-  // several ranks: the partial rows themselves are all-reduced (rows_mode) and the consumers keep
-  // their prologue re-reduction; the slot variants stay reachable through MI355OPT_FORCE_SLOT_PATH
-  const bool sharded = slot_mode(ctx);
-  const bool rows = rows_mode(ctx);
-  // direction-Gram fusion (mi_op::dirgram): one-pass Hessian, the Gram rows come from the direction kernel
-  const mi_dirgram *dgp = (!ctx->no_dirgram && H->dirgram && H->apply_dir) ? H->dirgram : nullptr;
-  // rows wider than 4 doubles (Stiefel p = 5 ... 8) have the one-pass operator in its recurrence form only (no
-  // preconditioner); with one, the operator keeps its two passes and the direction kernel its flat form
-  if (dgp && dgp->p > 4 && (pre != PRE_NONE || ctx->dirgram_direct)) dgp = nullptr;
-  MI_REQUIRE(!dgp || (dgp->p >= 1 && dgp->p <= kMaxP && dgp->n * (size_t)dgp->p == g->n),
-             "operator's direction-Gram description does not match the problem dimension");
-  // (default depth 3: depth 2 gives the same cfg2 step and -0.6 % on a cfg3 TNT run, DESIGN 3.3)
-  const int run_ahead = prm->run_ahead > 0 ? prm->run_ahead : 3;
-  const bool lockstep = (ctx->comm != nullptr && ctx->world_size > 1) || ctx->force_lockstep;
-
+  comm_halo_fold_drop(ctx);  // (nothing may be pending from an earlier solve: see ~StpcgBufs)
+  StpcgPlan plan;
+  MI_TRY(stpcg_plan(ctx, H, P, prm, g->n, observed, plan));
+  const StpcgPlan &pl = plan;
+  StpcgBufs b(ctx);
+  // (allocates the residual-halo buffers on first use; a rank that cannot must fail HERE, loudly, rather than take
+  // another collective sequence than its peers -- ADVICE r05)
+  if (pl.recur && !pl.folded && pl.dgp->halo_A) MI_TRY(comm_rprime_prepare(ctx, pl.dgp->halo_A, &b.rprime));
   // the failure word is per solve: a NaN residual in one solve must not condemn the object for the next
   if (P && P->fail_word) MI_HIP(hipMemsetAsync(P->fail_word, 0, sizeof(double), ctx->stream));
-
-  mi_vec *r = nullptr, *v = nullptr, *p = nullptr, *p2 = nullptr, *Hp = nullptr;
-  MI_TRY(mi_vec_create(ctx, n, &r));
-  MI_TRY(mi_vec_create(ctx, n, &p));
-  MI_TRY(mi_vec_create(ctx, n, &Hp));
-  if (pre != PRE_NONE) MI_TRY(mi_vec_create(ctx, n, &v));
-  double *vd = (pre == PRE_NONE) ? r->d : v->d;  // v aliases r when P is absent (:231,383)
-  const double *pred = P ? P->data : nullptr;
-
-  size_t tcap = 0;
-  if (trace && trace->cap) {
-    if (ctx->trace_cap < trace->cap) {
-      if (ctx->trace_dev) MI_HIP(hipFree(ctx->trace_dev));
-      MI_HIP(hipMalloc((void **)&ctx->trace_dev, 4 * trace->cap * sizeof(double)));
-      ctx->trace_cap = trace->cap;
-    }
-    tcap = ctx->trace_cap;  // layout stride
-  }
-
+  MI_TRY(stpcg_bufs(ctx, pl, g, H, P, prm, s_out, trace, b));
   ctx->cg_deferred = false;  // (a result nobody collected is superseded)
   ctx->cg_deferred_seq = 0;
   ctx->epoch++;
   ctx->status->word = 0;
   ctx->status->epoch = ctx->epoch;
-
-  CgSetup cfg{prm->Delta, prm->kappa_fgr, prm->theta, prm->epsilon,
-              (unsigned long long)prm->max_iterations};
-  CgConst cc{prm->Delta, prm->Delta * prm->Delta, prm->epsilon, (unsigned long long)prm->max_iterations, 0ull, 0ull};
-  hipStream_t st = ctx->stream;
-  const int grid = (pre == PRE_BLOCK3) ? grid_for(ctx, n / 3, 2) : grid_for(ctx, n, 4);
-  {
-    const size_t n2 = n >> 1, step = (size_t)grid * kBlock;
-    cc.rag0 = (n2 / step) * step;
-    cc.rag_per = (n2 - cc.rag0 + (size_t)grid - 1) / (size_t)grid;
-  }
-  // recurrence form of the direction Gram: needs v == r (no preconditioner)
-  const bool recur = dgp && pre == PRE_NONE && !ctx->dirgram_direct;
-  const int gns = dgp ? dgp->p * (dgp->p + 1) / 2 : 0;
-  const DirGramArgs dga = dgp ? DirGramArgs{dgp->X, dgp->Y, dgp->S, ctx->partials2,
-                                            recur ? ctx->scalars + SLOT_GDIR : nullptr, gns}
-                              : DirGramArgs{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  const int sp = (dgp && !recur) ? dgp->p : 0;  // row form of k_cg_pupdate only in the direct form
-  const int kc = recur ? dir_comps(dgp->p) : 3;  // components of the operator's partial rows
-  double *slots_g = ctx->scalars + SLOT_GRAM;    // slot file of the recurrence form (kc <= 16 doubles)
-  double *slots_a = ctx->scalars + SLOT_CG, *slots_b = ctx->scalars + SLOT_CG + 4;
-  CgState *st0 = ctx->cg, *st1 = ctx->cg1;
-  // Several ranks through the peer-memory layer, unpreconditioned recurrence form (the cfg2 / cfg4 hot loop): the two
-  // scalar exchanges of an iteration are folded into the prologues of their consumers (no exchange kernels).  Every
-  // other combination keeps the separate exchange kernels.
-  // (the folded exchange carries at most kIpcVals = 16 values: p <= 4)
-  const bool folded = sharded && recur && kc <= kIpcVals && comm_fold_enabled(ctx) && !ctx->force_slot_path;
-  // r'-halo form (Config::halo_rprime): the halo rows of r' travel with the <r,v> all-reduce, halo(p') is formed locally
-  bool rprime = false;
-  if (recur && !folded && dgp->halo_A) {
-    // (allocates the residual-halo buffers on first use; a rank that cannot must fail HERE, loudly, rather than take
-    // another collective sequence than its peers -- ADVICE r05)
-    const int st_rp = comm_rprime_prepare(ctx, dgp->halo_A, &rprime);
-    if (st_rp != MI_OK) {
-      mi_vec_destroy(r);
-      mi_vec_destroy(p);
-      mi_vec_destroy(Hp);
-      if (v) mi_vec_destroy(v);
-      return st_rp;
-    }
-  }
-  // unpreconditioned recurrence form: initialisation and the first direction's Gram rows in one pass
-  // (k_cg_init_dirgram); one rank, nothing to exchange: G(p0), G(r0) set by k_cg_scalar_init itself
-  const bool init_fused = recur && n == dgp->n * (size_t)dgp->p;
-  const bool gdir_in_scalar_init = recur && !sharded && !rows;
-  // opt-in experiment: the two-kernel step (k_cg_step2; one rank, Stiefel(n,3) in the window form)
-  // (an observed solve keeps the plain three-kernel step: the two-kernel step has no point between the operator and
-  // the update, the early-s form is an experiment, and the deferred-s form would show the observer of an odd pass an s
-  // that is one term short)
-  const bool twok = ctx->cfg.two_kernel_step && recur && dgp->twok && dgp->p == 3 && !sharded && !rows && !lockstep &&
-                    init_fused && gdir_in_scalar_init && !observed;
-  // (the early-s form: single context, v = r or any plain vector, at most three elements per thread, <= 512 rows)
-  const bool early = !sharded && !rows && sp == 0 && ctx->cfg.early_s && grid <= 512 &&
-                     cc.rag0 <= 2ull * (size_t)grid * kBlock && (n >> 1) < ((size_t)1 << 31) && !observed;
-  // deferred-s form (k_cg_pupdate_ds): single context, flat direction kernel; the direction lives in two buffers that
-  // swap every iteration -- `p` is the current one wherever this function names it
-  const bool defer = !sharded && !rows && !lockstep && !twok && sp == 0 && !early && ctx->cfg.defer_s && !observed;
-  CgState *st_final = st0;
-  double *tr = tcap ? ctx->trace_dev : nullptr;
-  int ret = MI_OK;
-  if (defer) {
-    const int st_p2 = mi_vec_create(ctx, n, &p2);
-    if (st_p2 != MI_OK) {
-      mi_vec_destroy(r);
-      mi_vec_destroy(p);
-      mi_vec_destroy(Hp);
-      if (v) mi_vec_destroy(v);
-      return st_p2;
-    }
-  }
-  ctx->cg_live = st0;
-  // observed solve: k_cg_peek's four words land at the head of the pinned state copy (free until the final read-back)
-  unsigned long long *peek_dev = nullptr;
-  if (observed) {
-    const hipError_t e = hipHostGetDevicePointer((void **)&peek_dev, ctx->cg_host, 0);
-    if (e != hipSuccess) {
-      mi_vec_destroy(r);
-      mi_vec_destroy(p);
-      mi_vec_destroy(p2);
-      mi_vec_destroy(Hp);
-      mi_vec_destroy(v);
-      ctx->cg_live = nullptr;
-      return hip_fail(e, "stpcg observer: device address of the pinned words", __FILE__, __LINE__);
-    }
-  }
-
-#define CG_CHECK(expr)   \
-  do {                   \
-    int _s = (expr);     \
-    if (_s != MI_OK) {   \
-      ret = _s;          \
-      goto cleanup;      \
-    }                    \
-  } while (0)
-#define LAUNCH_PRE(KERNEL, ...)                                                                   \
-  switch (pre) {                                                                                  \
-    case PRE_NONE: hipLaunchKernelGGL((KERNEL<PRE_NONE>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__); break;     \
-    case PRE_DIAG: hipLaunchKernelGGL((KERNEL<PRE_DIAG>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__); break;     \
-    case PRE_BLOCK3: hipLaunchKernelGGL((KERNEL<PRE_BLOCK3>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL((KERNEL<PRE_EXTERNAL>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__); break;       \
-  }
-#define LAUNCH_UPDATE(KN, FS)                                                                          \
-  switch (pre) {                                                                                       \
-    case PRE_NONE: hipLaunchKernelGGL((KN<PRE_NONE, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;     \
-    case PRE_DIAG: hipLaunchKernelGGL((KN<PRE_DIAG, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;     \
-    case PRE_BLOCK3: hipLaunchKernelGGL((KN<PRE_BLOCK3, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-    default: hipLaunchKernelGGL((KN<PRE_EXTERNAL, FS>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break;       \
-  }
-
-  // --- initialisation -----------------------------------------------------------------------
-  if (init_fused) {
-    KScope ks(ctx, MI_K_CG_INIT);
-    const size_t nrows = dgp->n;
-#define INIT_DG(SPV)                                                                                       \
-  hipLaunchKernelGGL(k_cg_init_dirgram<SPV>, dim3(grid), dim3(StBlk<SPV>::threads), 0, st, nrows, (const double *)g->d, \
-                     r->d, p->d, s_out->d, ctx->partials_b, dga)
-    switch (dgp->p) {
-      case 1: INIT_DG(1); break;
-      case 2: INIT_DG(2); break;
-      case 3: INIT_DG(3); break;
-      case 4: INIT_DG(4); break;
-      case 5: INIT_DG(5); break;
-      case 6: INIT_DG(6); break;
-      case 7: INIT_DG(7); break;
-      default: INIT_DG(8); break;
-    }
-#undef INIT_DG
-  } else {
-    KScope ks(ctx, MI_K_CG_INIT);
-    LAUNCH_PRE(k_cg_init, n, (const double *)g->d, pred, r->d, vd, p->d, s_out->d, ctx->partials_b);
-  }
-  if (pre == PRE_EXTERNAL) {
-    if (P->apply_project) CG_CHECK(P->apply_project(P, r, v, prm->constraint_At));  // (v, lambda) = P(r); r -= A' lambda
-    else CG_CHECK(P->apply(P, r, v));
-    hipLaunchKernelGGL(k_cg_dot_rv<true>, dim3(grid), dim3(kBlock), 0, st, n, (const CgState *)st0,
-                       (const double *)r->d, (const double *)v->d, p->d, ctx->partials_b);
-  }
-  if (dgp) {
-    const size_t nrows = dgp->n;
-    if (!init_fused) {
-      switch (dgp->p) {
-        case 1: hipLaunchKernelGGL(k_cg_dirgram<1>, dim3(grid), dim3(kBlock), 0, st, nrows, (const double *)p->d, dga); break;
-        case 2: hipLaunchKernelGGL(k_cg_dirgram<2>, dim3(grid), dim3(kBlock), 0, st, nrows, (const double *)p->d, dga); break;
-        case 3: hipLaunchKernelGGL(k_cg_dirgram<3>, dim3(grid), dim3(kBlock), 0, st, nrows, (const double *)p->d, dga); break;
-        case 4: hipLaunchKernelGGL(k_cg_dirgram<4>, dim3(grid), dim3(kBlock), 0, st, nrows, (const double *)p->d, dga); break;
-        case 5: hipLaunchKernelGGL(k_cg_dirgram<5>, dim3(grid), dim3(StBlk<5>::threads), 0, st, nrows, (const double *)p->d, dga); break;
-        case 6: hipLaunchKernelGGL(k_cg_dirgram<6>, dim3(grid), dim3(StBlk<6>::threads), 0, st, nrows, (const double *)p->d, dga); break;
-        case 7: hipLaunchKernelGGL(k_cg_dirgram<7>, dim3(grid), dim3(StBlk<7>::threads), 0, st, nrows, (const double *)p->d, dga); break;
-        default: hipLaunchKernelGGL(k_cg_dirgram<8>, dim3(grid), dim3(StBlk<8>::threads), 0, st, nrows, (const double *)p->d, dga); break;
-      }
-    }
-    if (recur && !gdir_in_scalar_init) {
-      if (sharded) CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials2, grid, gns, slots_g));
-      else if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials2, gns));
-      hipLaunchKernelGGL(k_cg_gdir_init, dim3(1), dim3(kBlock), 0, st, (const double *)ctx->partials2, grid, gns,
-                         (const double *)slots_g, sharded ? 1 : 0, dga.gdir);
-    }
-  }
-  if (sharded) {
-    CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials_b, grid, 1, slots_b));
-    hipLaunchKernelGGL(k_cg_scalar_init<true>, dim3(1), dim3(kBlock), 0, st, st0, cfg,
-                       (const double *)ctx->partials_b, grid, (const double *)slots_b, ctx->status_dev,
-                       (const double *)nullptr, 0, 0, (double *)nullptr);
-  } else {
-    if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials_b, 1));
-    hipLaunchKernelGGL(k_cg_scalar_init<false>, dim3(1), dim3(kBlock), 0, st, st0, cfg,
-                       (const double *)ctx->partials_b, grid, (const double *)slots_b, ctx->status_dev,
-                       (const double *)ctx->partials2, grid, gns, gdir_in_scalar_init ? dga.gdir : (double *)nullptr);
-  }
-  {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) CG_CHECK(hip_fail(e, "stpcg init launch", __FILE__, __LINE__));
-  }
+  ctx->cg_live = b.st0;
+  MI_TRY(stpcg_setup(ctx, pl, b));
 
   // --- main loop: speculative enqueue with bounded run-ahead -----------------------------------
-  {
-    size_t hvp = 0;
-    bool observed_last_pass = false;
-    for (size_t k = 0; k < prm->max_iterations; ++k) {
-      // throttle: at most run_ahead launches ahead of the device
-      uint64_t w = ctx->status->word;
-      while (!observed && !(w & 1) && k > (w >> 1) + (uint64_t)run_ahead) {  // (an observed solve never runs ahead)
-        cpu_relax();
-        w = ctx->status->word;
-      }
-      if (w & 1) {
-        // One rank: stop as soon as the exit is seen.  Several ranks: every enqueued iteration carries
-        // collectives, so all ranks must enqueue the SAME number -- exactly (launches at exit) + run_ahead,
-        // a function of the replicated device state only, not of when this host happened to look.  (No
-        // rank can get past that count unknowingly: the throttle holds it until the exit is published.)
-        if (!lockstep || k >= (w >> 1) + (uint64_t)run_ahead) break;
-      }
-
-      // r06: re-anchor the recurrence form's G(p), G(r) by the direct form every cfg.reanchor iterations (the count is
-      // the loop index: the same on every rank, so the exchanges it carries stay matched across ranks)
-      if (recur && !twok && ctx->cfg.reanchor > 0 && k > 0 && k % (size_t)ctx->cfg.reanchor == 0) {
-        const size_t nrows = dgp->n;
-        if (dgp->p <= 4) {
-          // rows of <= 4 doubles: both Grams from ONE pass over X, Y, p, r and one (all-)reduction of 2 gns components
-          switch (dgp->p) {
-            case 1: hipLaunchKernelGGL(k_cg_dirgram2<1>, dim3(grid), dim3(kBlock), 0, st, nrows, (const CgState *)st0, (const double *)p->d, (const double *)r->d, dga); break;
-            case 2: hipLaunchKernelGGL(k_cg_dirgram2<2>, dim3(grid), dim3(kBlock), 0, st, nrows, (const CgState *)st0, (const double *)p->d, (const double *)r->d, dga); break;
-            case 3: hipLaunchKernelGGL(k_cg_dirgram2<3>, dim3(grid), dim3(kBlock), 0, st, nrows, (const CgState *)st0, (const double *)p->d, (const double *)r->d, dga); break;
-            default: hipLaunchKernelGGL(k_cg_dirgram2<4>, dim3(grid), dim3(kBlock), 0, st, nrows, (const CgState *)st0, (const double *)p->d, (const double *)r->d, dga); break;
-          }
-          if (sharded) CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials2, grid, 2 * gns, slots_g));
-          else if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials2, 2 * gns));
-          hipLaunchKernelGGL(k_cg_gdir_anchor, dim3(1), dim3(kBlock), 0, st, (const double *)ctx->partials2, grid, gns,
-                             (const double *)slots_g, sharded ? 1 : 0, (const CgState *)st0, dga.gdir + SLOT_GDIR_P,
-                             dga.gdir);
-        } else {
-          for (int which = 0; which < 2; ++which) {
-            const double *vec = which == 0 ? p->d : r->d;
-            switch (dgp->p) {
-              case 5: hipLaunchKernelGGL(k_cg_dirgram<5>, dim3(grid), dim3(StBlk<5>::threads), 0, st, nrows, vec, dga); break;
-              case 6: hipLaunchKernelGGL(k_cg_dirgram<6>, dim3(grid), dim3(StBlk<6>::threads), 0, st, nrows, vec, dga); break;
-              case 7: hipLaunchKernelGGL(k_cg_dirgram<7>, dim3(grid), dim3(StBlk<7>::threads), 0, st, nrows, vec, dga); break;
-              default: hipLaunchKernelGGL(k_cg_dirgram<8>, dim3(grid), dim3(StBlk<8>::threads), 0, st, nrows, vec, dga); break;
-            }
-            if (sharded) CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials2, grid, gns, slots_g));
-            else if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials2, gns));
-            hipLaunchKernelGGL(k_cg_gdir_anchor, dim3(1), dim3(kBlock), 0, st, (const double *)ctx->partials2, grid, gns,
-                               (const double *)slots_g, sharded ? 1 : 0, (const CgState *)st0,
-                               dga.gdir + (which == 0 ? SLOT_GDIR_P : 0), (double *)nullptr);
-          }
-        }
-      }
-
-      // Hp = H(p) (:294) + partial rows of <p,Hp>, <Hp,Hp>, <p,p> in ctx->partials
-      int nparts = 0;
-      if (twok) {  // two launches per iteration; the state ping-pongs between st0 and st1 ACROSS iterations
-        CgState *cur = (k & 1) ? st1 : st0, *nxt = (k & 1) ? st0 : st1;
-        ctx->cg_live = cur;
-        ctx->twok_r = r->d;
-        CG_CHECK(H->apply_dir(H, p, Hp, -2, &nparts));
-        ctx->twok_r = nullptr;
-        ++hvp;
-        {
-          KScope ks(ctx, MI_K_CG_UPDATE);
-          hipLaunchKernelGGL(k_cg_step2<6>, dim3(grid), dim3(kBlock), 0, st, n, cc, (const CgState *)cur, nxt,
-                             (const double *)ctx->partials, nparts, (const double *)Hp->d, r->d, p->d, s_out->d,
-                             ctx->status_dev, tr, tcap, dga);
-        }
-        st_final = nxt;
-        continue;
-      }
-      if (dgp) {
-        CG_CHECK(H->apply_dir(H, p, Hp, recur ? -1 : grid, &nparts));
-      } else if (H->apply_dots) {
-        CG_CHECK(H->apply_dots(H, p, Hp, &nparts));
-      } else {
-        CG_CHECK(H->apply(H, p, Hp));
-        CG_CHECK(launch_dot3_partials(ctx, n, p->d, Hp->d, &nparts));
-      }
+  CgState *st_final = b.st0;
+  size_t hvp = 0;
+  for (size_t k = 0; k < prm->max_iterations; ++k) {
+    // throttle: at most run_ahead launches ahead of the device
+    uint64_t w = ctx->status->word;
+    while (!observed && !(w & 1) && k > (w >> 1) + (uint64_t)pl.run_ahead) {  // (an observed solve never runs ahead)
+      cpu_relax();
+      w = ctx->status->word;
+    }
+    if (w & 1) {
+      // One rank: stop as soon as the exit is seen.  Several ranks: every enqueued iteration carries
+      // collectives, so all ranks must enqueue the SAME number -- exactly (launches at exit) + run_ahead,
+      // a function of the replicated device state only, not of when this host happened to look.  (No
+      // rank can get past that count unknowingly: the throttle holds it until the exit is published.)
+      if (!pl.lockstep || k >= (w >> 1) + (uint64_t)pl.run_ahead) break;
+    }
+    if (pl.reanchor && k > 0 && k % (size_t)pl.reanchor == 0) MI_TRY(stpcg_reanchor(ctx, pl, b));
+    if (pl.twok) {
+      MI_TRY(stpcg_step2(ctx, pl, b, k, &st_final));
       ++hvp;
-      if (observed) {
-        // alpha_k and the decisions of :300-362 to the host: one small kernel and one polled wait per pass
-        ctx->host_syncs++;
-        unsigned long long *flag = nullptr;
-        const unsigned long long seq = poll_begin(ctx, &flag);
-        {
-          KScope ks(ctx, MI_K_CG_SCALAR_A);
-          hipLaunchKernelGGL(k_cg_peek, dim3(1), dim3(kBlock), 0, st, cc, (const CgState *)st0,
-                             (const double *)ctx->partials, nparts, peek_dev, seq ? flag : (unsigned long long *)nullptr,
-                             seq);
-        }
-        {
-          hipError_t e = hipGetLastError();
-          if (e != hipSuccess) CG_CHECK(hip_fail(e, "stpcg observer peek launch", __FILE__, __LINE__));
-        }
-        CG_CHECK(poll_finish(ctx, seq, "stpcg observer peek"));
-        const volatile unsigned long long *pk = reinterpret_cast<const volatile unsigned long long *>(ctx->cg_host);
-        const int mode_in = (int)pk[0], mode_a = (int)pk[1];
-        // (this pass's operator is already enqueued -- hvp_calls counts ENQUEUED passes, here as in the un-observed solve --
-        // unless the test of the status word at the top of the loop happened to see the exit first)
-        if (mode_in == CG_DONE) break;  // the last pass's B-step (or the initialisation) ended the solve: :285, :290
-        if (mode_a == CG_RUN) {
-          double alpha_k;
-          const unsigned long long abits = pk[2];
-          memcpy(&alpha_k, &abits, sizeof(alpha_k));
-          ctx->cg_in_observer = true;
-          const int stop = observer(observer_user, (size_t)pk[3], s_out, r, v ? v : r, p, alpha_k);
-          ctx->cg_in_observer = false;
-          if (stop) {
-            hipLaunchKernelGGL(k_cg_user_stop, dim3(1), dim3(64), 0, st, st0, ctx->status_dev);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) CG_CHECK(hip_fail(e, "stpcg observer stop launch", __FILE__, __LINE__));
-            break;
-          }
-        } else {
-          observed_last_pass = true;  // kernel-of-H or boundary exit inside this pass: the reference does not call either
-        }
-      }
-      // (deferred-s form, odd k: a term of s is pending, and a boundary step is the direction kernel's to apply behind it)
-      const bool sigma_later = defer && (k & 1);
-#define UPD_ARGS                                                                                      \
-  n, cc, (const CgState *)st0, st1, (const double *)ctx->partials, nparts,                              \
-      (const double *)(recur ? slots_g : slots_a), (const double *)p->d, (const double *)Hp->d, pred,  \
-      s_out->d, r->d, vd, ctx->partials_b, dga
-      if (recur) {
-        // 3 dots + the Gram rows of Hp in one reduction (and one exchange across ranks)
-        // KN: k_cg_update, or its 80-SGPR twin for the instantiations that need more (see above; 16 components always do)
-#define UPD_RECUR(KN, K16, FS, FT, FV)                                                                             \
-  switch (kc) {                                                                                                    \
-    case 4: hipLaunchKernelGGL((KN<PRE_NONE, FS, 4, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break;   \
-    case 6: hipLaunchKernelGGL((KN<PRE_NONE, FS, 6, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break;   \
-    case 9: hipLaunchKernelGGL((KN<PRE_NONE, FS, 9, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break;   \
-    default: hipLaunchKernelGGL((K16<PRE_NONE, FS, 16, FT>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, FV); break; \
-  }
-  // p = 5 ... 8: 18, 24, 31, 39 components (3 + p (p + 1) / 2).  Never folded (the host keeps the separate exchange for
-  // them), and launched from the uncapped kernel: 39 reduced values per thread do not fit the 64 vector registers the
-  // two-workgroups-per-CU twins are held to
-#define UPD_WIDE(KN, FS)                                                                                                    \
-  switch (kc) {                                                                                                             \
-    case 18: hipLaunchKernelGGL((KN<PRE_NONE, FS, 18, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-    case 24: hipLaunchKernelGGL((KN<PRE_NONE, FS, 24, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-    case 31: hipLaunchKernelGGL((KN<PRE_NONE, FS, 31, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-    default: hipLaunchKernelGGL((KN<PRE_NONE, FS, 39, NoFold>), dim3(grid), dim3(kBlock), 0, st, UPD_ARGS, NoFold{}); break; \
-  }
-        if (kc > 16) {
-          if (sharded) CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials, nparts, kc, slots_g));
-          else if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials, kc));
-          KScope ks(ctx, MI_K_CG_UPDATE);
-          if (sharded) { UPD_WIDE(k_cg_update, true); } else if (sigma_later) { UPD_WIDE(k_cg_update_ns, false); } else { UPD_WIDE(k_cg_update, false); }
-        } else if (sharded && folded) {
-          // the sum over the ranks completes in the kernel's own prologue (comm_ipc.h): no exchange kernel
-          const FoldArgs fold_a = comm_fold_next(ctx);
-          KScope ks(ctx, MI_K_CG_UPDATE);
-          UPD_RECUR(k_cg_update_s80, k_cg_update_s80, false, FoldArgs, fold_a);
-        } else if (sharded) {
-          CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials, nparts, kc, slots_g));
-          KScope ks(ctx, MI_K_CG_UPDATE);
-          UPD_RECUR(k_cg_update_s80, k_cg_update_s80, true, NoFold, NoFold{});
-        } else {
-          if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials, kc));
-          KScope ks(ctx, MI_K_CG_UPDATE);
-          if (sigma_later) { UPD_RECUR(k_cg_update_ns, k_cg_update_ns_s80, false, NoFold, NoFold{}); }
-          else { UPD_RECUR(k_cg_update, k_cg_update_s80, false, NoFold, NoFold{}); }
-        }
-#undef UPD_RECUR
-#undef UPD_WIDE
-      } else if (sharded) {
-        CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials, nparts, 3, slots_a));
-        KScope ks(ctx, MI_K_CG_UPDATE);
-        LAUNCH_UPDATE(k_cg_update, true);
-      } else {
-        if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials, 3));
-        KScope ks(ctx, MI_K_CG_UPDATE);
-        if (sigma_later) { LAUNCH_UPDATE(k_cg_update_ns, false); } else { LAUNCH_UPDATE(k_cg_update, false); }
-      }
-#undef UPD_ARGS
-      if (pre == PRE_EXTERNAL) {
-        if (P->apply_project) CG_CHECK(P->apply_project(P, r, v, prm->constraint_At));  // :386,403
-        else CG_CHECK(P->apply(P, r, v));  // v = P(r) (:386)
-        hipLaunchKernelGGL(k_cg_dot_rv<false>, dim3(grid), dim3(kBlock), 0, st, n, (const CgState *)st1,
-                           (const double *)r->d, (const double *)v->d, p->d, ctx->partials_b);
-      }
-#define PUPD_ARGS                                                                                          \
-  n, cc, (const CgState *)st1, st0, (const double *)ctx->partials_b, grid, (const double *)slots_b,        \
-      (const double *)vd, p->d, s_out->d, ctx->status_dev, tr, tcap, dga
-#define PUPD(KN, FS, SPV) \
-  hipLaunchKernelGGL((KN<FS, SPV>), dim3(grid), dim3(kBlock), 0, st, PUPD_ARGS, NoFold{})
-  // (KN0 / KN1: the kernel for rows of 0 / 1 doubles, the two forms that count on 8 waves per SIMD; wider rows are
-  // bound by their vector registers)
-#define LAUNCH_PUPD(KN0, KN1, FS)               \
-  switch (sp) {                                 \
-    case 0: PUPD(KN0, FS, 0); break;            \
-    case 1: PUPD(KN1, FS, 1); break;            \
-    case 2: PUPD(k_cg_pupdate, FS, 2); break;   \
-    case 3: PUPD(k_cg_pupdate, FS, 3); break;   \
-    default: PUPD(k_cg_pupdate, FS, 4); break;  \
-  }
-      if (sharded && folded) {
-        const FoldArgs fold_b = comm_fold_next(ctx);  // (folded <=> recurrence form <=> sp == 0)
-        // ... and the halo exchange of the NEXT Hessian pass rides in this kernel's stores of the new direction
-        FoldPush fp{fold_b, HaloPush{}};
-        const bool push = dgp && dgp->halo_A && k + 1 < prm->max_iterations &&
-                          comm_halo_fold_next(ctx, dgp->halo_A, dgp->p, p->d, &fp.h);
-        KScope ks(ctx, MI_K_CG_PUPDATE);
-        if (push)
-          hipLaunchKernelGGL((k_cg_pupdate_s80<false, 0, FoldPush>), dim3(grid), dim3(kBlock), 0, st, PUPD_ARGS, fp);
-        else
-          hipLaunchKernelGGL((k_cg_pupdate_s80<false, 0, FoldArgs>), dim3(grid), dim3(kBlock), 0, st, PUPD_ARGS, fold_b);
-      } else if (sharded) {
-        CG_CHECK(reduce_rows_allreduce(ctx, ctx->partials_b, grid, 1, slots_b));
-        if (rprime) CG_CHECK(comm_rprime_exchange(ctx, dgp->halo_A, dgp->p, r->d, nullptr, 0));
-        KScope ks(ctx, MI_K_CG_PUPDATE);
-        LAUNCH_PUPD(k_cg_pupdate_s80, k_cg_pupdate_s80, true);
-      } else {
-        if (rows && rprime) CG_CHECK(comm_rprime_exchange(ctx, dgp->halo_A, dgp->p, r->d, ctx->partials_b, 1));
-        else if (rows) CG_CHECK(comm_allreduce_rows(ctx, ctx->partials_b, 1));
-        KScope ks(ctx, MI_K_CG_PUPDATE);
-#define PUPD_DS(FLUSH)                                                                                                  \
-  hipLaunchKernelGGL(k_cg_pupdate_ds<FLUSH>, dim3(grid), dim3(kBlock), 0, st, n, cc, (const CgState *)st1, st0,          \
-                     (const double *)ctx->partials_b, grid, (const double *)vd, (const double *)p->d, p2->d, s_out->d, \
-                     ctx->status_dev, tr, tcap, dga)
-        if (early) {
-          hipLaunchKernelGGL(k_cg_pupdate_early, dim3(grid), dim3(kBlock), 0, st, n, cc, (const CgState *)st1, st0,
-                             (const double *)ctx->partials_b, grid, (const double *)vd, p->d, s_out->d, ctx->status_dev, tr,
-                             tcap, dga);
-        } else if (defer && (k & 1)) {
-          PUPD_DS(true);
-          std::swap(p, p2);
-        } else if (defer && k + 1 < prm->max_iterations) {
-          PUPD_DS(false);
-          std::swap(p, p2);
-        } else {  // (deferred-s form: the last enqueued iteration is an even one)
-          LAUNCH_PUPD(k_cg_pupdate, k_cg_pupdate_s80, false);
-        }
-#undef PUPD_DS
-      }
-      if (rprime && (sharded || rows)) {
-        const double *hr = nullptr;
-        double *hp = nullptr;
-        size_t cnt = 0;
-        comm_rprime_buffers(ctx, dgp->halo_A, dgp->p, &hr, &hp, &cnt);
-        if (cnt) {
-          const int hg = (int)std::max<size_t>(1, std::min<size_t>((cnt + 255) / 256, 512));
-          hipLaunchKernelGGL(k_halo_dir, dim3(hg), dim3(256), 0, st, (const CgState *)st0, hr, hp, cnt);
-        }
-        comm_rprime_mark(ctx, dgp->halo_A, dgp->p, p->d);
-      }
-#undef LAUNCH_PUPD
-#undef PUPD
-#undef PUPD_ARGS
-      if (observed_last_pass) break;  // (the pass just enqueued ends the solve: no further peek)
+      continue;
     }
-    result->hvp_calls = hvp;
-    comm_halo_fold_drop(ctx);  // (a push behind the last enqueued iteration has no reader)
+    int nparts = 0;
+    MI_TRY(stpcg_operator(ctx, pl, b, &nparts));
+    ++hvp;
+    ObserverSays says = OBS_GO_ON;
+    if (observed) MI_TRY(stpcg_observe(ctx, pl, b, observer, observer_user, nparts, &says));
+    if (says == OBS_STOP) break;
+    MI_TRY(stpcg_astep(ctx, pl, b, k, nparts));
+    if (pl.pre == PRE_EXTERNAL) MI_TRY(stpcg_precondition(ctx, pl, b, false));
+    MI_TRY(stpcg_bstep(ctx, pl, b, k));
+    if (says == OBS_LAST_PASS) break;
   }
+  result->hvp_calls = hvp;
+  comm_halo_fold_drop(ctx);  // (a push behind the last enqueued iteration has no reader)
+  MI_TRY(stpcg_readback(ctx, pl, b, st_final, trace, result));
+  b.ok = true;  // (no synchronisation on this exit)
+  return MI_OK;
+}
 
-  // --- read back the final state ----------------------------------------------------------------
-  if (prm->defer_result && !(trace && trace->cap) && !observed) {
-    // the copy travels behind the solve; whoever waits for the stream next (or mi_stpcg_collect) completes it
-    hipError_t e = hipSuccess;
-    *precon_fail_host(ctx) = 0.0;
-    ctx->cg_deferred_seq = result_to_host(ctx, st_final, P);
-    if (!ctx->cg_deferred_seq) {
-      if (!ctx->cg_deferred_ev) e = hipEventCreateWithFlags(&ctx->cg_deferred_ev, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipMemcpyAsync(ctx->cg_host, st_final, sizeof(CgState), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess && P && P->fail_word)
-        e = hipMemcpyAsync(precon_fail_host(ctx), P->fail_word, sizeof(double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipEventRecord(ctx->cg_deferred_ev, st);
+}  // namespace
+
+extern "C" {
+
+int mi_stpcg_collect(mi_ctx *ctx, mi_stpcg_result *result) {
+  MI_REQUIRE(ctx && result, "null argument");
+  MI_REQUIRE(ctx->cg_deferred, "mi_stpcg_collect: no deferred solve is pending on this context");
+  ctx->cg_deferred = false;
+  if (ctx->cg_deferred_seq) {
+    const unsigned long long seq = ctx->cg_deferred_seq;
+    ctx->cg_deferred_seq = 0;
+    if (__atomic_load_n(ctx->poll_flag, __ATOMIC_ACQUIRE) < seq) {
+      ctx->host_syncs++;
+      MI_TRY(poll_finish(ctx, seq, "stpcg deferred read-back"));
     }
-    if (e != hipSuccess) CG_CHECK(hip_fail(e, "stpcg deferred read-back", __FILE__, __LINE__));
-    ctx->cg_deferred = true;
-    ctx->cg_deferred_hvp = result->hvp_calls;
-    result->update_step_M_norm = 0;
-    result->num_iterations = 0;
-    result->exit_reason = -1;
-    result->rv_final = 0;
-    result->precon_status = 0;
   } else {
-    hipError_t e = hipSuccess;
-    *precon_fail_host(ctx) = 0.0;
-    ctx->host_syncs++;
-    if (const unsigned long long seq = result_to_host(ctx, st_final, P)) {
-      CG_CHECK(poll_finish(ctx, seq, "stpcg read-back"));
-    } else {
-      e = hipMemcpyAsync(ctx->cg_host, st_final, sizeof(CgState), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess && P && P->fail_word)
-        e = hipMemcpyAsync(precon_fail_host(ctx), P->fail_word, sizeof(double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e != hipSuccess) CG_CHECK(hip_fail(e, "stpcg read-back", __FILE__, __LINE__));
+    hipError_t e = hipEventQuery(ctx->cg_deferred_ev);
+    if (e == hipErrorNotReady) {
+      e = hipEventSynchronize(ctx->cg_deferred_ev);
+      ctx->host_syncs++;
     }
-    CG_CHECK(precon_fail_check(ctx, result));
-    {
-      int ipc_err = 0;
-      (void)mi_comm_ipc_error(ctx, &ipc_err);
-      if (ipc_err) {
-        set_error("a wait in the peer-memory exchange layer timed out: the result of this solve is invalid");
-        ret = MI_ERR_COMM;
-        goto cleanup;
-      }
-    }
-    const CgState &f = *ctx->cg_host;
-    result->update_step_M_norm = f.M_norm;
-    result->num_iterations = (size_t)f.k;
-    result->exit_reason = f.exit_reason;
-    result->rv_final = f.rv;
-    if (trace && trace->cap) {
-      const size_t len = f.k < trace->cap ? (size_t)f.k : trace->cap;
-      trace->len = len;
-      double *dst[4] = {trace->alpha, trace->beta, trace->kappa, trace->rv};
-      for (int c = 0; c < 4; ++c)
-        if (dst[c] && len) {
-          e = hipMemcpy(dst[c], ctx->trace_dev + (size_t)c * tcap, len * sizeof(double),
-                        hipMemcpyDeviceToHost);
-          if (e != hipSuccess) CG_CHECK(hip_fail(e, "stpcg trace copy", __FILE__, __LINE__));
-        }
-    }
+    if (e != hipSuccess) return hip_fail(e, "stpcg deferred read-back", __FILE__, __LINE__);
   }
-
-cleanup:
-#undef CG_CHECK
-#undef LAUNCH_PRE
-#undef LAUNCH_UPDATE
-  ctx->cg_live = nullptr;
-  // a folded halo push nobody consumed must not outlive the solve on ANY exit: p is a recycled pool pointer, and the
-  // next solve's first Hessian pass would match the stale (A, p, V) entry, skip the real exchange and wait for a flag
-  // that never comes (r04, ADVICE: an error exit between comm_halo_fold_next and the pass used to leave it set)
-  comm_halo_fold_drop(ctx);
-  if (ret != MI_OK) (void)hipStreamSynchronize(st);
-  mi_vec_destroy(r);
-  mi_vec_destroy(p);
-  mi_vec_destroy(p2);
-  mi_vec_destroy(Hp);
-  mi_vec_destroy(v);
-  return ret;
+  result->hvp_calls = ctx->cg_deferred_hvp;
+  return stpcg_result_from_host(ctx, result);
 }
 
 int mi_stpcg_observer_available(mi_ctx *ctx, const char **why) {
