@@ -588,6 +588,17 @@ MI_API int mi_debug_so3n_info(const mi_so3n *q, size_t out[6]);
  * a workgroup budget, a CU count and the matrix's far stride in rows (0: none); needs no GPU */
 MI_API int mi_debug_window_runs(int ntiles, int max_wgs, int num_cu, size_t far_stride, int *bounds_out, int cap,
                                 int *nb_out);
+/* host-only, read-only: the launch plan of the Stiefel one-pass Hessian for rows of p doubles and a gram_count (-1: the
+ * recurrence form, -2: that of the two-kernel step, >= 0: Gram rows of the direction kernel); needs no GPU.
+ *   traits   = {packed copy, window words, 16-bit window words, window chunks, widest slice, pure far stride D,
+ *               common far stride, halo buffer, row-sharded} of the matrix
+ *   switches = {NO_WINDOW, NO_FAR_COMPUTED, WORDS16, WIDE_QUAD, WIDE_WINDOW, NO_WIN_BOUNDS, uniform grid, slot mode,
+ *               the two-kernel step's residual is set} of the context
+ *   out      = {form (0 k_st_hess_fused plain, 1 its window form, 2 k_st_hess_widewin, 3 k_st_hess_wide,
+ *               4 k_st_hess_wideq), FROM_SLOTS, HALO, RECUR, PK, HW, FAR, TWOK, block size, dynamic LDS bytes, run table
+ *               wanted, halo exchange first, Gram reduction first, the gram_count = -2 form exists}
+ * A combination the library treats as an internal error is an error here too (MI_ERR_INVALID_ARGUMENT). */
+MI_API int mi_debug_stiefel_hess_form(int p, int gram_count, const size_t traits[9], const int switches[9], int out[14]);
 MI_API int mi_debug_set_rank(mi_ctx *ctx, int world_size, int rank);
 MI_API int mi_debug_csr_set_halo(mi_csr *A, int p, const double *halo_rows_host); /* (need_lo+need_hi) x p */
 /* Measurement hook: average microseconds of `reps` back-to-back applications of the operator in the fused form

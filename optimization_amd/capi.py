@@ -268,6 +268,22 @@ def window_runs(ntiles, max_wgs, num_cu=256, far_stride=0):
     return np.array(buf[:nb.value + 1], dtype=np.int64)
 
 
+def stiefel_hess_form_fn():
+    """mi_debug_stiefel_hess_form, bound on first use (an older experiment build loaded through MI355OPT_LIB lacks it)"""
+    fn = load().mi_debug_stiefel_hess_form
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    return fn
+
+
+def stiefel_hess_form(p, gram_count, traits, switches):
+    """launch plan of the Stiefel one-pass Hessian (host-only, mi_debug_stiefel_hess_form): the 14 numbers of `out`,
+    or None where the library answers with an error"""
+    out = (C.c_int * 14)()
+    st = stiefel_hess_form_fn()(p, gram_count, (C.c_size_t * 9)(*traits), (C.c_int * 9)(*switches), out)
+    return list(out) if st == MI_OK else None
+
+
 def csr_shard_plan(n_global, world_size, rank, row_starts, col_global):
     """Host-only (no GPU): (col_local int32, need_lo, need_hi) for this rank's slab of a row-sharded matrix."""
     L = load()

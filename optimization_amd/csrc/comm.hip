@@ -326,7 +326,7 @@ bool comm_halo_fold_next(mi_ctx *ctx, const mi_csr *A, int p, const double *V, H
   if (ctx->world_size <= 1 || !ctx->comm || !A) return false;
   Comm *c = (Comm *)ctx->comm;
   if (!(c->ipc_enabled && c->fold && A->halo_in_arena)) return false;
-  if (A->halo_lo + A->halo_hi + A->send_lo + A->send_hi == 0) return false;
+  if (!csr_row_sharded(A)) return false;
   const int rk = ctx->rank, ws = ctx->world_size;
   const size_t lo = rk > 0 ? A->send_lo * p : 0, hi = rk + 1 < ws ? A->send_hi * p : 0, nd = A->n * (size_t)p;
   // the pushing kernel stores double2: every boundary of the exchange must fall on one
@@ -387,7 +387,7 @@ int comm_halo_exchange_or_wait(mi_ctx *ctx, const mi_csr *A, int p, const double
 
 int comm_halo_exchange(mi_ctx *ctx, const mi_csr *A, int p, const double *V) {
   if (ctx->world_size <= 1 || !ctx->comm) return MI_OK;
-  if (A->halo_lo + A->halo_hi + A->send_lo + A->send_hi == 0) return MI_OK;
+  if (!csr_row_sharded(A)) return MI_OK;
   Comm *c = (Comm *)ctx->comm;
   c->pushed = {};
   c->formed = {};
@@ -446,7 +446,7 @@ int comm_rprime_prepare(mi_ctx *ctx, const mi_csr *A, bool *enabled) {
   if (!ctx->cfg.halo_rprime || ctx->world_size <= 1 || !ctx->comm || !A || !A->halo) return MI_OK;
   // (a rank without halo rows of its own still takes part in its neighbours' exchanges: every rank of a slab partition
   // with more than one slab sends or receives something, so this test is the same everywhere)
-  if (A->halo_lo + A->halo_hi + A->send_lo + A->send_hi == 0) return MI_OK;
+  if (!csr_row_sharded(A)) return MI_OK;
   // the r' rows need a buffer pair of their own where the layer in use can reach it: inside the arena for peer stores
   // (the same decision on every rank: same sizes, same allocation order), anywhere for RCCL
   const Comm *c = (const Comm *)ctx->comm;

@@ -2091,7 +2091,7 @@ namespace {
 bool spmm_win_ok(const mi_csr *A) {
   const bool no_win = A->ctx->cfg.no_spmm_win;
   return A->pk && A->wk && A->win_chunks > 0 && A->win_chunks <= 2 && !no_win && !A->ctx->uniform_grid &&
-         A->halo_lo + A->halo_hi + A->send_lo + A->send_hi == 0 && A->n * 8 < ((size_t)1 << 32);
+         !csr_row_sharded(A) && A->n * 8 < ((size_t)1 << 32);
 }
 
 // Y = A X in window form, 8 columns per pass.  theta_host != nullptr: the fused residual form (k_spmm_colmajor_win<..,
@@ -2111,7 +2111,7 @@ int spmm_win_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const doub
   const size_t lds = (size_t)kSpmmWinCols * ((size_t)nc * 64 + 1) * sizeof(double);
   const bool hw7 = A->win_head <= 7, wc1 = A->win_chunks == 1, res = theta_host != nullptr;
   const void *fn = nullptr;
-  const bool fard = A->win_far_pure > 0 && A->win_far_pure < ((size_t)1 << 31) && !ctx->cfg.no_far_computed;
+  const bool fard = csr_far_computed(ctx, A);
 #define PICK3(HWV, WCV, FV, RV) fn = (const void *)k_spmm_colmajor_win<kSpmmWinCols, HWV, WCV, FV, RV>
 #define PICK(HWV, WCV)                                                        \
   if (res) { if (fard) PICK3(HWV, WCV, true, true); else PICK3(HWV, WCV, false, true); } \
@@ -2120,8 +2120,7 @@ int spmm_win_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const doub
   else { if (hw7) { PICK(7, 2) } else { PICK(8, 2) } }
 #undef PICK
 #undef PICK3
-  static int occ_cache[2][2][2][2] = {};
-  int &occ = occ_cache[hw7 ? 0 : 1][wc1 ? 0 : 1][fard ? 1 : 0][res ? 1 : 0];
+  int &occ = ctx->spmm_win_occ[hw7 ? 0 : 1][wc1 ? 0 : 1][fard ? 1 : 0][res ? 1 : 0];
   if (occ == 0) {
     int nbk = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, fn, kWinBlock, lds);
@@ -2170,7 +2169,7 @@ int spmm_win_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const doub
 bool spmm_sweep_ok(const mi_csr *A) {
   return A->pk && A->win_far_pure >= (size_t)(2 * kSwRows) && A->win_far_pure < ((size_t)1 << 22) && A->win_chunks > 0 &&
          A->win_chunks <= 2 && A->win_head <= 8 && !A->ctx->cfg.no_spmm_sweep && !A->ctx->uniform_grid &&
-         A->halo_lo + A->halo_hi + A->send_lo + A->send_hi == 0 && A->n < ((size_t)1 << 31) && !A->ctx->comm;
+         !csr_row_sharded(A) && A->n < ((size_t)1 << 31) && !A->ctx->comm;
 }
 
 int spmm_sweep_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const double *theta_host, double *Rd,
@@ -2279,7 +2278,7 @@ int mi_csr_spmm_colmajor_blocks(const mi_csr *A, const mi_panel_blocks *X, mi_ve
     const double *s0 = X->block[i]->d, *s1 = s0 + (size_t)X->cols[i] * A->n;
     MI_REQUIRE(Y->d + (size_t)k * A->n <= s0 || Y->d >= s1, "SpMM input and output must not alias");
   }
-  const bool sharded = A->halo_lo + A->halo_hi + A->send_lo + A->send_hi > 0;
+  const bool sharded = csr_row_sharded(A);
   if (!sharded && spmm_win_ok(A) && A->n > 0) {
     touch(Y);
     KScope ks(ctx, MI_K_SPMM);
@@ -2300,7 +2299,7 @@ int mi_csr_spmm_colmajor(const mi_csr *A, int k, const mi_vec *X, mi_vec *Y) {
   MI_REQUIRE(X->d != Y->d, "SpMM input and output must not alias");
   touch(Y);
   mi_ctx *ctx = A->ctx;
-  if (A->halo_lo + A->halo_hi + A->send_lo + A->send_hi > 0) {
+  if (csr_row_sharded(A)) {
     // Row-sharded matrix (8(e): "LOBPCG: row-shard S"): four columns at a time through the row-major sharded
     // product -- its halo exchange is sized for p <= 4 -- at the price of two extra passes over those columns.
     // COLLECTIVE: every rank of the communicator makes the same call.

@@ -81,6 +81,17 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
     case 4: { constexpr int P = 4; __VA_ARGS__; } break;            \
     default: set_error("internal: narrow-row kernel asked for p = %d", p); return MI_ERR_INTERNAL; \
   }
+// ... on one of three values of an integer template parameter NAME (the last one: every other x)
+#define DISPATCH_3(x, NAME, A, B, C, ...)                   \
+  switch (x) {                                              \
+    case A: { constexpr int NAME = A; __VA_ARGS__; } break; \
+    case B: { constexpr int NAME = B; __VA_ARGS__; } break; \
+    default: { constexpr int NAME = C; __VA_ARGS__; } break; \
+  }
+// ... and on a boolean template parameter: the statement runs with NAME as a compile-time constant
+#define DISPATCH_FLAG(x, NAME, ...)                       \
+  if (x) { constexpr bool NAME = true; __VA_ARGS__; }     \
+  else { constexpr bool NAME = false; __VA_ARGS__; }
 
 // Host-visible progress word written by the device (fine-grained pinned memory).
 struct HostStatus {
@@ -239,6 +250,11 @@ struct mi_ctx {
   // pinned word and the host polls it -- the wake-up of hipStreamSynchronize costs more than the kernel
   unsigned long long *poll_flag = nullptr;
   unsigned long long poll_seq = 0;
+  // what the runtime was asked once about a kernel instantiation.  Per context, because a context is one device and
+  // both the answer and the attribute belong to the device:
+  int st_win_occ[4][2][2][2] = {};      // stiefel.hip window_occupancy: [p][halo][head > 7][computed far columns], 0 = not asked
+  bool st_widewin_lds[5][2][2] = {};    // stiefel.hip k_st_hess_widewin<p - 4, head > 7, computed far>: dynamic-LDS attribute set
+  int spmm_win_occ[2][2][2][2] = {};    // lobpcg.hip spmm_win_launch: [head > 7][two chunks][computed far][residual form]
   // timing
   mi::KTimer ktime[MI_K_COUNT];
   std::vector<hipEvent_t> event_pool;
@@ -633,6 +649,16 @@ struct mi_csr {
 };
 
 namespace mi {
+// the matrix is one slab of a row-sharded one: it receives halo rows or sends boundary rows
+inline bool csr_row_sharded(const mi_csr *A) { return A->halo_lo + A->halo_hi + A->send_lo + A->send_hi > 0; }
+// computed far columns: matrices whose far entries are all at row +- D with D in 32 bits; the window kernels then work
+// the far columns out instead of loading them from wfar (opt-out: NO_FAR_COMPUTED)
+inline bool far_computed(size_t win_far_pure, bool no_far_computed) {
+  return win_far_pure > 0 && win_far_pure < ((size_t)1 << 31) && !no_far_computed;
+}
+inline bool csr_far_computed(const mi_ctx *ctx, const mi_csr *A) {
+  return far_computed(A->win_far_pure, ctx->cfg.no_far_computed);
+}
 // W = A V - (*scale) W with partials of |W|^2 (p = 1): see mi_op::apply_sub_scaled
 int csr_spmv_sub_scaled(const mi_csr *A, const mi_vec *V, const double *scale, const int *mode, const int *gate,
                         mi_vec *W, double *partials, int *nparts);

@@ -552,11 +552,8 @@ int csr_spmm_launch(const mi_csr *A, int p, const double *V, double *W) {
   const bool no_stream = ctx->cfg.no_spmm_stream;
   if (!no_stream && p >= 1 && p <= kMaxP && sell_stream_ok(A, p)) {
     const int sgrid = (int)std::min<size_t>(ngroups, 256);  // one workgroup per CU, one round
-#define SS(HL, PKV) \
-  DISPATCH_P(p, hipLaunchKernelGGL((k_spmm_stream<P, HL, PKV>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, view, V, W))
-    if (A->halo) { if (A->pk) { SS(true, true); } else { SS(true, false); } }
-    else { if (A->pk) { SS(false, true); } else { SS(false, false); } }
-#undef SS
+    DISPATCH_FLAG(A->halo != nullptr, HL, DISPATCH_FLAG(A->pk != nullptr, PK, DISPATCH_P(p,
+        hipLaunchKernelGGL((k_spmm_stream<P, HL, PK>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, view, V, W))));
     MI_HIP(hipGetLastError());
     return MI_OK;
   }

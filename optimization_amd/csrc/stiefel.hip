@@ -1200,12 +1200,9 @@ int launch_spmm_gram(mi_ctx *ctx, const mi_csr *A, int p, const CgState *st, con
     if (!ctx->uniform_grid && grid > 256) grid = 256;  // one workgroup per CU, one round
     if (p > 4 && !ctx->uniform_grid)                   // 256-thread workgroups: two per CU
       grid = (int)std::max<size_t>(1, std::min<size_t>((A->nslices + 3) / 4, std::min<size_t>(2 * (size_t)ctx->num_cu, 2 * (size_t)ctx->max_grid)));
-#define SG(HL, PKV)                                                                                            \
-  DISPATCH_P(p, hipLaunchKernelGGL((k_st_spmm_gram_stream<P, HL, PKV>), dim3(grid), dim3(StBlk<P>::threads), 0, ctx->stream, \
-                                   view, st, V, X, S, Z, ctx->partials2))
-    if (A->halo) { if (A->pk) { SG(true, true); } else { SG(true, false); } }
-    else { if (A->pk) { SG(false, true); } else { SG(false, false); } }
-#undef SG
+    DISPATCH_FLAG(A->halo != nullptr, HL, DISPATCH_FLAG(A->pk != nullptr, PK, DISPATCH_P(p,
+        hipLaunchKernelGGL((k_st_spmm_gram_stream<P, HL, PK>), dim3(grid), dim3(StBlk<P>::threads), 0, ctx->stream, view, st,
+                           V, X, S, Z, ctx->partials2))));
   } else {
     DISPATCH_P4(p, hipLaunchKernelGGL(k_st_spmm_gram<P>, dim3(grid), dim3(kBlock), 0, ctx->stream, view, st, V,
                                       X, S, Z, ctx->partials2));
@@ -1225,16 +1222,9 @@ int launch_finish(mi_ctx *ctx, size_t n, int p, const CgState *st, const double 
   if (rows_mode(ctx)) MI_TRY(comm_allreduce_rows(ctx, ctx->partials2, nsym(p)));
   if (sharded) MI_TRY(sharded_reduce(ctx, count, nsym(p), slots));
   KScope ks(ctx, MI_K_STIEFEL_FINISH_DOTS);
-#define FIN(D, F)                                                                                       \
-  DISPATCH_P(p, hipLaunchKernelGGL((k_st_finish<P, D, F>), dim3(grid), dim3(StBlk<P>::threads), 0, ctx->stream, n, st, \
-                                   X, Z, Vin, (const double *)ctx->partials2, count,                    \
-                                   (const double *)slots, M_out, out, ctx->partials))
-  if (dots) {
-    if (sharded) { FIN(true, true); } else { FIN(true, false); }
-  } else {
-    if (sharded) { FIN(false, true); } else { FIN(false, false); }
-  }
-#undef FIN
+  DISPATCH_FLAG(dots, D, DISPATCH_FLAG(sharded, F, DISPATCH_P(p,
+      hipLaunchKernelGGL((k_st_finish<P, D, F>), dim3(grid), dim3(StBlk<P>::threads), 0, ctx->stream, n, st, X, Z, Vin,
+                         (const double *)ctx->partials2, count, (const double *)slots, M_out, out, ctx->partials))));
   if (nparts) *nparts = grid;
   MI_HIP(hipGetLastError());
   return MI_OK;
@@ -1305,251 +1295,248 @@ int rq_apply_dots(mi_op *self, const mi_vec *in, mi_vec *out, int *nparts) {
   return rq_apply_common(self, in, out, true, nparts);
 }
 
-// one-pass Hessian for STPCG: the direction kernel left `gram_count` partial rows of sym(Y'in - (X'in) S)
+// ---- one-pass Hessian for STPCG: the direction kernel left `gram_count` partial rows of sym(Y'in - (X'in) S) ----
+// A plan (which of the five kernel forms runs and with which template selectors: plain facts in, no HIP call), the
+// kernel a plan names, and one function that enqueues it.
+enum StHessForm {
+  ST_HESS_PLAIN = 0,    // k_st_hess_fused<P, ., ., ., ., 0>: the streaming form of rows of <= 4 doubles
+  ST_HESS_WINDOW = 1,   // k_st_hess_fused<P, false, ., true, true, HW, FAR>: its LDS-window form (p <= 3)
+  ST_HESS_WIDEWIN = 2,  // k_st_hess_widewin<P, HW, FARD>: the window form of rows of 4 ... 8 doubles
+  ST_HESS_WIDE = 3,     // k_st_hess_wide<P, HALO, PK>: rows of 5 ... 8 doubles, one lane per row
+  ST_HESS_WIDEQ = 4     // k_st_hess_wideq<P, HALO, PK>: the same in the quad layout (4 lanes per row)
+};
+
+// what the plan reads of a matrix and of its context
+struct StHessTraits {
+  bool pk, wk, wk16;  // the matrix has a packed copy, window words, their 16-bit form
+  int win_chunks, win_head;
+  size_t win_far_pure, win_far_stride;
+  bool halo, row_sharded;  // a halo buffer exists; csr_row_sharded
+  bool no_window, no_far_computed, words16, no_win_bounds, uniform_grid, slot_mode, twok_r;
+  int wide_quad, wide_window;
+};
+StHessTraits st_hess_traits(const mi_ctx *ctx, const mi_csr *A) {
+  const Config &c = ctx->cfg;
+  return {A->pk != nullptr, A->wk != nullptr, A->wk16 != nullptr, A->win_chunks, A->win_head, A->win_far_pure,
+          A->win_far_stride, A->halo != nullptr, csr_row_sharded(A), c.no_window, c.no_far_computed, c.words16,
+          c.no_win_bounds, ctx->uniform_grid, slot_mode(ctx), ctx->twok_r != nullptr, c.wide_quad, c.wide_window};
+}
+
+struct StHessPlan {
+  int form = ST_HESS_PLAIN;
+  // template selectors of the form's kernel (what a form does not have stays false / 0)
+  bool from_slots = false, halo = false, recur = false, pk = false, twok = false;
+  int hw = 0;   // entries per slice of the window forms (7 or 8); 0: no window
+  int far = 0;  // far columns of the window forms: 0 loaded, 1 computed, 2 computed + 16-bit words
+  int block = kBlock;
+  size_t lds_bytes = 0;  // dynamic LDS
+  int wc = 0;            // window half-width in chunks as the kernel is told (WinView)
+  bool fard = false;     // computed far columns (WinView::far_d)
+  bool run_table = false;    // the launch asks window_bounds for planned runs
+  bool exchange = false;     // comm_halo_exchange_or_wait precedes the launch
+  bool gram_reduce = false;  // the Gram rows are reduced first: across ranks in rows mode, into slots where from_slots
+  const char *error = nullptr;  // why there is no plan (the function then returns MI_ERR_INVALID_ARGUMENT)
+};
+
+int st_hess_plan(int p, int gram_count, const StHessTraits &t, StHessPlan *out) {
+  StHessPlan &pl = *out = StHessPlan();
+  const auto fail = [&](const char *why) { pl.error = why; return (int)MI_ERR_INVALID_ARGUMENT; };
+  if (p < 1 || p > kMaxP) return fail("internal: the one-pass Hessian exists for rows of 1 ... 8 doubles");
+  pl.fard = far_computed(t.win_far_pure, t.no_far_computed);
+  const int hw = t.win_head <= 7 ? 7 : 8;
+  // r06: the wide rows' window form where the matrix has one (packed, window of <= 2 chunks, no halo, one context) --
+  // p = 4 ... 7 by default (at p = 8 the ring's rows are 64 bytes apart: 16-way LDS bank conflicts, and the quad layout
+  // is there); MI355OPT_WIDE_WINDOW = 0 / 1 forces it off / on for every width
+  const bool wide_window = (t.wide_window < 0 ? p <= 7 && !(t.wide_quad > 0) : t.wide_window != 0) && t.pk && t.wk &&
+                           t.win_chunks > 0 && t.win_chunks <= 2 && !t.halo && !t.uniform_grid && !t.no_window &&
+                           !t.row_sharded;
+  // p = 5 ... 8: the recurrence form through k_st_hess_wide / k_st_hess_wideq / k_st_hess_widewin.  p = 4 has no window
+  // form of its own (ring + far slots of 4 x 4 workgroups: see WIN in k_st_hess_fused); in the recurrence form it takes
+  // the wide rows' (k_st_hess_widewin<4>, dynamic LDS sized for the matrix's own window) where that one applies
+  if (p > 4 || (p == 4 && gram_count == -1 && wide_window)) {
+    if (gram_count >= 0) return fail("internal: rows wider than 4 doubles take the one-pass Hessian in its recurrence form only");
+    pl.recur = true;
+    if (wide_window) {
+      pl.form = ST_HESS_WIDEWIN, pl.block = kWinBlock, pl.run_table = true;
+      pl.pk = true, pl.hw = hw, pl.far = pl.fard ? 1 : 0, pl.wc = t.win_chunks;
+      pl.lds_bytes = (size_t)((2 * kWinWaves + 2 * pl.wc) * 64 + 1 + kWinFarRows) * (size_t)(p == 8 ? 9 : p) * sizeof(double);
+      return MI_OK;
+    }
+    // the quad layout where it measured faster (St(1e6,p), profiles/r05_wide_quad_ab.txt: p = 8: 82 vs 98 us; p = 5, 6, 7:
+    // 80 / 73 / 93 vs 59 / 69 / 83 us for one lane per row); MI355OPT_WIDE_QUAD=0 / 1 forces either form
+    const bool quad = t.wide_quad < 0 ? p == 8 : t.wide_quad != 0;
+    pl.form = quad ? ST_HESS_WIDEQ : ST_HESS_WIDE, pl.block = kWideBlock, pl.exchange = true;
+    pl.halo = t.halo, pl.pk = t.pk;
+    // (runs cut to the far stride; tiles = 4 slices)
+    pl.run_table = !t.uniform_grid && t.win_far_stride && !t.no_win_bounds && kWideWaves == kWinWaves;
+    return MI_OK;
+  }
+  pl.recur = gram_count < 0, pl.halo = t.halo, pl.exchange = true, pl.gram_reduce = !pl.recur;
+  // the window form when the matrix qualifies (decided at creation, sparse.hip build_window); p = 4 does not fit
+  pl.wc = (t.no_window || p > 3 || !t.wk) ? 0 : t.win_chunks;
+  const bool win = pl.recur && pl.wc > 0;  // (recurrence form only: the unpreconditioned solve)
+  // 16-bit words: opt-in (MI355OPT_WORDS16=1).  On cfg2 they shorten the pass by ~1 us (25.9 -> 24.9 us) by halving
+  // the matrix stream (28 -> 16 MB of 132 MB); the pass then runs at the same ~5.5 TB/s of a smaller total.
+  const bool w16 = pl.fard && !t.halo && t.wk16 && t.words16;
+  pl.form = win ? ST_HESS_WINDOW : ST_HESS_PLAIN, pl.block = win ? kWinBlock : kBlock;
+  pl.run_table = win && !t.uniform_grid;  // planned runs of whole tiles (sparse.hip window_bounds)
+  pl.twok = gram_count == -2;  // the two-kernel step (opt-in experiment): stpcg.hip asks for it only where twok says it exists
+  if (pl.twok && !(win && pl.fard && !t.halo && !w16 && p == 3 && t.twok_r))
+    return fail("internal: two-kernel step without its Hessian form");
+  // window form: far columns loaded / computed (some of them halo columns of a row shard) / computed with 16-bit words
+  if (win) pl.pk = true, pl.hw = hw, pl.far = w16 ? 2 : pl.fard ? 1 : 0;
+  else pl.pk = t.pk, pl.from_slots = t.slot_mode && !pl.recur;
+  return MI_OK;
+}
+// mi_dirgram::twok: apply_dir(gram_count = -2) exists -- p = 3, window form with computed far columns, one rank
+bool st_hess_twok_exists(int p, StHessTraits t) {
+  StHessPlan pl;
+  t.twok_r = true;
+  return !t.uniform_grid && st_hess_plan(p, -2, t, &pl) == MI_OK && pl.twok;
+}
+
+// The instantiations of the three kernel templates that exist: exactly those a plan can name.
+template <int P, bool F, bool HL, bool RC, bool PK, int HW, int FAR, bool TWOK>
+const void *st_fused_fn() {
+  constexpr bool plain = HW == 0 && FAR == 0 && !TWOK && !(RC && F);
+  constexpr bool window = HW > 0 && !F && RC && PK && !(FAR == 2 && HL) && (!TWOK || (P == 3 && FAR == 1 && !HL));
+  if constexpr (plain || window) return (const void *)k_st_hess_fused<P, F, HL, RC, PK, HW, FAR, TWOK>;
+  else return nullptr;
+}
+template <int P, int HW, bool FARD>
+const void *st_widewin_fn() {
+  if constexpr (P >= 4 && HW > 0) return (const void *)k_st_hess_widewin<P, HW, FARD>;
+  else return nullptr;
+}
+template <int P, bool HL, bool PK, bool QUAD>
+const void *st_wide_fn() {
+  if constexpr (P < 5) return nullptr;
+  else if constexpr (QUAD) return (const void *)k_st_hess_wideq<P, HL, PK>;
+  else return (const void *)k_st_hess_wide<P, HL, PK>;
+}
+// entries per slice of a window kernel (0: none) and its far-column form
+#define DISPATCH_HW(hw, ...) DISPATCH_3(hw, HW, 0, 7, 8, __VA_ARGS__)
+#define DISPATCH_FAR(far, ...) DISPATCH_3(far, FAR, 0, 1, 2, __VA_ARGS__)
+int st_hess_kernel(int p, const StHessPlan &pl, const void **fn) {
+  *fn = nullptr;
+  if (pl.form == ST_HESS_WIDEWIN) {
+    DISPATCH_P(p, DISPATCH_HW(pl.hw, DISPATCH_FLAG(pl.far != 0, FARD, *fn = st_widewin_fn<P, HW, FARD>())));
+  } else if (pl.form == ST_HESS_WIDE || pl.form == ST_HESS_WIDEQ) {
+    DISPATCH_P(p, DISPATCH_FLAG(pl.halo, HL, DISPATCH_FLAG(pl.pk, PK, DISPATCH_FLAG(pl.form == ST_HESS_WIDEQ, QUAD,
+                                                                                   *fn = st_wide_fn<P, HL, PK, QUAD>()))));
+  } else {
+    DISPATCH_P4(p, DISPATCH_HW(pl.hw, DISPATCH_FAR(pl.far, DISPATCH_FLAG(pl.from_slots, F, DISPATCH_FLAG(pl.halo, HL,
+        DISPATCH_FLAG(pl.recur, RC, DISPATCH_FLAG(pl.pk, PK, DISPATCH_FLAG(pl.twok, TWOK,
+            *fn = st_fused_fn<P, F, HL, RC, PK, HW, FAR, TWOK>()))))))));
+  }
+  if (!*fn) {
+    set_error("internal: the one-pass Hessian has no kernel of form %d for p = %d", pl.form, p);
+    return MI_ERR_INTERNAL;
+  }
+  return MI_OK;
+}
 
 // resident workgroups per CU of the window instantiation that will run (registers + LDS), asked of the runtime once
-// per instantiation: the launch plan must fit one round
-int window_occupancy(int p, bool halo, int hw, bool fard) {
-  static int cache[4][2][2][2] = {};
-  int &slot = cache[p][halo ? 1 : 0][hw == 7 ? 0 : 1][fard ? 1 : 0];
+// per instantiation and context: the launch plan must fit one round.  (The 16-bit-word and two-kernel variants are
+// planned with the answer for their base form, FAR = 1.)
+int window_occupancy(mi_ctx *ctx, int p, StHessPlan pl) {
+  int &slot = ctx->st_win_occ[p][pl.halo ? 1 : 0][pl.hw == 7 ? 0 : 1][pl.fard ? 1 : 0];
   if (slot == 0) {
+    pl.far = pl.fard ? 1 : 0, pl.twok = false;
+    const void *fn = nullptr;
     int nb = 0;
-    hipError_t e = hipErrorUnknown;
-#define OCC(PV, HL, HWV, FV)                                                                                   \
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_st_hess_fused<PV, false, HL, true, true, HWV, FV>,  \
-                                                   kWinBlock, 0)
-#define OCC_F(PV, HL, HWV) \
-  if (fard) OCC(PV, HL, HWV, 1); else OCC(PV, HL, HWV, 0)
-#define OCC_P(PV)                                                \
-  if (halo) { if (hw == 7) { OCC_F(PV, true, 7); } else { OCC_F(PV, true, 8); } } \
-  else { if (hw == 7) { OCC_F(PV, false, 7); } else { OCC_F(PV, false, 8); } }
-    if (p == 1) { OCC_P(1) } else if (p == 2) { OCC_P(2) } else { OCC_P(3) }
-#undef OCC_P
-#undef OCC_F
-#undef OCC
-    slot = (e == hipSuccess && nb > 0) ? nb : 1;
+    const bool ok = st_hess_kernel(p, pl, &fn) == MI_OK &&
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kWinBlock, 0) == hipSuccess;
+    slot = (ok && nb > 0) ? nb : 1;
     (void)hipGetLastError();
   }
   return slot;
 }
 
-// r06: the window form where the matrix has one (packed, window of <= 2 chunks, no halo, one context) -- p = 4 ... 7 by
-// default (at p = 8 the ring's rows are 64 bytes apart: 16-way LDS bank conflicts, and the quad layout is there);
-// MI355OPT_WIDE_WINDOW = 0 / 1 forces it off / on for every width
-static bool wide_window_form(const mi_ctx *ctx, const mi_csr *A, int p) {
-  return (ctx->cfg.wide_window < 0 ? p <= 7 && !(ctx->cfg.wide_quad > 0) : ctx->cfg.wide_window != 0) && A->pk && A->wk &&
-         A->win_chunks > 0 && A->win_chunks <= 2 && !A->halo && !ctx->uniform_grid && !ctx->cfg.no_window &&
-         A->halo_lo + A->halo_hi + A->send_lo + A->send_hi == 0;
-}
-
-// p = 5 ... 8 (and p = 4 in window form): the recurrence form through k_st_hess_wide / k_st_hess_widewin
-int rq_apply_dir_wide(mi_stiefel_rq *q, const mi_vec *in, mi_vec *out, int gram_count, int *nparts) {
-  mi_ctx *ctx = q->ctx;
-  const mi_csr *A = q->A;
-  const int p = q->p;
-  MI_REQUIRE(gram_count < 0, "internal: rows wider than 4 doubles take the one-pass Hessian in its recurrence form only");
-  // 256-thread workgroups, as many per CU as the kernel is held to (WideWaves<P>: one wave per SIMD each): one resident
-  // round, at most kMaxRows partial rows; several ranks in rows mode need exactly kMaxGrid of them
-  const size_t wgs = (A->nslices + kWideWaves - 1) / kWideWaves;
-  // the quad layout where it measured faster (St(1e6,p), profiles/r05_wide_quad_ab.txt: p = 8: 82 vs 98 us; p = 5, 6, 7:
-  // 80 / 73 / 93 vs 59 / 69 / 83 us for one lane per row); MI355OPT_WIDE_QUAD=0 / 1 forces either form
-  const bool quad = ctx->cfg.wide_quad < 0 ? p == 8 : ctx->cfg.wide_quad != 0;
-  const int resident = ctx->num_cu * (quad ? MI_WIDE_QUAD_WAVES : p <= 7 ? MI_WIDE_WAVES : 2);
-  int grid = ctx->uniform_grid ? kMaxGrid : (int)std::max<size_t>(1, std::min<size_t>(wgs, std::min(resident, kMaxRows)));
-  if (!ctx->uniform_grid && ctx->max_grid < kMaxGrid) grid = std::min(grid, ctx->max_grid);
-  const int *bounds = nullptr;
-  if (!ctx->uniform_grid && A->win_far_stride && !ctx->cfg.no_win_bounds && kWideWaves == kWinWaves)
-    MI_TRY(window_bounds(ctx, A, grid, (int)wgs, &grid, &bounds));  // (runs cut to the far stride; tiles = 4 slices)
-  const bool winform = wide_window_form(ctx, A, p);
-  MI_REQUIRE(p > 4 || winform, "internal: p = 4 takes the wide rows' kernel in its window form only");
-  if (winform) {
-    const int wc = A->win_chunks, nc = 2 * kWinWaves + 2 * wc;
-    const bool fard = A->win_far_pure > 0 && A->win_far_pure < ((size_t)1 << 31) && !ctx->cfg.no_far_computed;
-    const size_t lds_bytes = (size_t)(nc * 64 + 1 + kWinFarRows) * (size_t)(p == 8 ? 9 : p) * sizeof(double);
-    const void *fn = nullptr;
-#define WW(PV, HWV) fn = fard ? (const void *)k_st_hess_widewin<PV, HWV, true> : (const void *)k_st_hess_widewin<PV, HWV, false>
-#define WW_P(PV) if (A->win_head <= 7) { WW(PV, 7); } else { WW(PV, 8); }
-    switch (p) {
-      case 4: WW_P(4); break;
-      case 5: WW_P(5); break;
-      case 6: WW_P(6); break;
-      case 7: WW_P(7); break;
-      default: WW_P(8); break;
-    }
-#undef WW_P
-#undef WW
-    static bool attr_set[5][2][2] = {};
-    bool &done = attr_set[p - 4][A->win_head <= 7 ? 0 : 1][fard ? 1 : 0];
-    if (!done) {  // (more than 64 KB of dynamic LDS needs the attribute)
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - 8 * 1024));
-      (void)hipGetLastError();
-      done = true;
-    }
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kWinBlock, lds_bytes) != hipSuccess || occ < 1) occ = 1;
-    (void)hipGetLastError();
-    const int ntiles = (int)((A->nslices + kWinWaves - 1) / kWinWaves);
-    int wgs = std::min(std::min(occ, p <= MI_WIDEWIN_3WAVES_UPTO ? 3 : 2) * ctx->num_cu, kMaxRows);
-    if (ctx->max_grid < kMaxGrid) wgs = std::min(wgs, ctx->max_grid);
-    int wgrid = 0;
-    const int *wbounds = nullptr;
-    MI_TRY(window_bounds(ctx, A, wgs, ntiles, &wgrid, &wbounds));
-    WinView wv{A->wk, A->wfar, wc, nc, A->win_zero, wbounds, fard ? (unsigned)A->win_far_pure : 0u, nullptr};
-    SellView view = sell_view(A);
-    const CgState *live = ctx->cg_live;
-    const double *inp = in->d, *Xp = q->X->d, *Yp = q->Y->d, *Sp = q->S_dev, *gd = ctx->scalars + SLOT_GDIR;
-    double *outp = out->d, *parts = ctx->partials;
-    void *args[] = {&view, &wv, &live, &inp, &Xp, &Yp, &Sp, &gd, &outp, &parts};
-    KScope ks(ctx, MI_K_STIEFEL_HESS_FUSED);
-    MI_HIP(hipLaunchKernel(fn, dim3(wgrid), dim3(kWinBlock), args, lds_bytes, ctx->stream));
-    *nparts = wgrid;
-    return MI_OK;
-  }
-  HaloWaitArg<true> hw_halo;
-  HaloWaitArg<false> hw_none;
-  MI_TRY(comm_halo_exchange_or_wait(ctx, A, p, in->d, &hw_halo.w));
-  hw_halo.halo_lo = (unsigned)A->halo_lo;
-  hw_halo.halo_hi = (unsigned)A->halo_hi;
-  SellView view = sell_view(A);  // after the exchange: it selects the halo buffer the rows landed in
-  KScope ks(ctx, MI_K_STIEFEL_HESS_FUSED);
-#define HWIDE_ARGS(HWARG)                                                                                               \
-  dim3(grid), dim3(kWideBlock), 0, ctx->stream, view, (const CgState *)ctx->cg_live, (const double *)in->d,             \
-      (const double *)q->X->d, (const double *)q->Y->d, (const double *)q->S_dev,                                       \
-      (const double *)(ctx->scalars + SLOT_GDIR), out->d, ctx->partials, HWARG, bounds
-#define HWIDE(PV, HL, PKV, HWARG)                                                                   \
-  if (quad) hipLaunchKernelGGL((k_st_hess_wideq<PV, HL, PKV>), HWIDE_ARGS(HWARG));                     \
-  else hipLaunchKernelGGL((k_st_hess_wide<PV, HL, PKV>), HWIDE_ARGS(HWARG))
-#define HWIDE_P(PV)                                                                                  \
-  if (A->halo) { if (A->pk) { HWIDE(PV, true, true, hw_halo); } else { HWIDE(PV, true, false, hw_halo); } } \
-  else { if (A->pk) { HWIDE(PV, false, true, hw_none); } else { HWIDE(PV, false, false, hw_none); } }
-  switch (p) {
-    case 5: HWIDE_P(5); break;
-    case 6: HWIDE_P(6); break;
-    case 7: HWIDE_P(7); break;
-    default: HWIDE_P(8); break;
-  }
-#undef HWIDE_P
-#undef HWIDE
-#undef HWIDE_ARGS
-  *nparts = grid;
-  MI_HIP(hipGetLastError());
-  return MI_OK;
-}
-
 int rq_apply_dir(mi_op *self, const mi_vec *in, mi_vec *out, int gram_count, int *nparts) {
   mi_stiefel_rq *q = (mi_stiefel_rq *)self->impl;
-  if (q->p > 4) return rq_apply_dir_wide(q, in, out, gram_count, nparts);
   mi_ctx *ctx = q->ctx;
   const mi_csr *A = q->A;
   const int p = q->p;
-  // p = 4 has no window form of its own (ring + far slots of 4 x 4 workgroups: see WIN below); in the recurrence form it
-  // takes the wide rows' (k_st_hess_widewin<4>, dynamic LDS sized for the matrix's own window) where that one applies
-  if (p == 4 && gram_count == -1 && wide_window_form(ctx, A, p)) return rq_apply_dir_wide(q, in, out, gram_count, nparts);
-  // one workgroup per CU and one round (the kernel needs > 64 VGPRs: a second round would only repeat the
-  // prologue); the rows mode of several ranks needs the uniform 512-row partial layout instead
-  constexpr int cap = 256;
-  int grid = uniform_grid(ctx, sell_groups(A));
-  if (!ctx->uniform_grid && grid > cap) grid = cap;
-  double *slots = ctx->scalars + SLOT_GRAM;
-  const bool recur = gram_count < 0;
-  const bool sharded = slot_mode(ctx) && !recur;
-  const bool halo = A->halo != nullptr;
-  // the window form when the matrix qualifies (decided at creation, sparse.hip build_window); p = 4 does not fit
-  const bool no_win = ctx->cfg.no_window;
-  const int wc = (no_win || p > 3 || !A->wk) ? 0 : A->win_chunks;
-  // (computed far columns: matrices whose far entries are all at row +- D, not sharded, D in 32 bits)
-  const bool fard = A->win_far_pure > 0 && A->win_far_pure < ((size_t)1 << 31) && !ctx->cfg.no_far_computed;
-  // 16-bit words: opt-in (MI355OPT_WORDS16=1).  On cfg2 they shorten the pass by ~1 us (25.9 -> 24.9 us) by halving
-  // the matrix stream (28 -> 16 MB of 132 MB); the pass then runs at the same ~5.5 TB/s of a smaller total.
-  const bool w16 = fard && !A->halo && A->wk16 && ctx->cfg.words16;
-  WinView wv{A->wk, A->wfar, wc, 2 * kWinWaves + 2 * wc, A->win_zero, nullptr, fard ? (unsigned)A->win_far_pure : 0u,
-             A->wk16};
-  const bool win = recur && wc > 0;
-  if (win && !ctx->uniform_grid) {  // planned runs of whole tiles (sparse.hip window_bounds)
-    const int ntiles = (int)((A->nslices + kWinWaves - 1) / kWinWaves);
-    // the workgroup budget: what is resident at once (one round), at most kMaxRows partial rows
-    const int occ = std::min(window_occupancy(p, halo, A->win_head <= 7 ? 7 : 8, fard), kWaves / kWinWaves);
-    int wgs = std::min(cap * occ, kMaxRows);
-    // (one-GPU rehearsals of several ranks: the pass waits for its neighbours in its prologue, so -- like the CG
-    // kernels -- it must leave room for their kernels while it does; mi_internal.h mi_ctx::max_grid)
-    if (ctx->max_grid < kMaxGrid) wgs = std::min(wgs, ctx->max_grid);  // (lowered explicitly: MI355OPT_MAX_GRID)
-    const int *bounds = nullptr;
-    MI_TRY(window_bounds(ctx, A, wgs, ntiles, &grid, &bounds));
-    wv.bounds = bounds;
+  StHessPlan pl;
+  if (const int st = st_hess_plan(p, gram_count, st_hess_traits(ctx, A), &pl)) {
+    set_error("%s", pl.error);
+    return st;
   }
-  const int block = win ? kWinBlock : kBlock;
-  HaloWaitArg<true> hw_halo;   // a push folded into the kernel that wrote `in`: the pass waits in its prologue
+  const void *fn = nullptr;
+  MI_TRY(st_hess_kernel(p, pl, &fn));
+  const bool capped = ctx->max_grid < kMaxGrid;  // (lowered explicitly: MI355OPT_MAX_GRID)
+  const int ntiles = (int)((A->nslices + kWinWaves - 1) / kWinWaves);
+  int grid = 0;
+  const int *bounds = nullptr;
+  if (pl.form == ST_HESS_WIDEWIN) {
+    bool &attr_set = ctx->st_widewin_lds[p - 4][pl.hw == 7 ? 0 : 1][pl.far];
+    if (!attr_set) {  // (more than 64 KB of dynamic LDS needs the attribute)
+      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - 8 * 1024));
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("k_st_hess_widewin<%d, %d, %s>: the dynamic LDS limit cannot be raised: %s", p, pl.hw,
+                  pl.far ? "true" : "false", hipGetErrorString(e));
+        return MI_ERR_HIP;
+      }
+      attr_set = true;
+    }
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kWinBlock, pl.lds_bytes) != hipSuccess || occ < 1) occ = 1;
+    (void)hipGetLastError();
+    int wgs = std::min(std::min(occ, p <= MI_WIDEWIN_3WAVES_UPTO ? 3 : 2) * ctx->num_cu, kMaxRows);
+    if (capped) wgs = std::min(wgs, ctx->max_grid);
+    MI_TRY(window_bounds(ctx, A, wgs, ntiles, &grid, &bounds));
+  } else if (pl.form == ST_HESS_WIDE || pl.form == ST_HESS_WIDEQ) {
+    // 256-thread workgroups, as many per CU as the kernel is held to (WideWaves<P>: one wave per SIMD each): one resident
+    // round, at most kMaxRows partial rows; several ranks in rows mode need exactly kMaxGrid of them
+    const size_t wgs = (A->nslices + kWideWaves - 1) / kWideWaves;
+    const int resident = ctx->num_cu * (pl.form == ST_HESS_WIDEQ ? MI_WIDE_QUAD_WAVES : p <= 7 ? MI_WIDE_WAVES : 2);
+    grid = ctx->uniform_grid ? kMaxGrid : (int)std::max<size_t>(1, std::min<size_t>(wgs, std::min(resident, kMaxRows)));
+    if (!ctx->uniform_grid && capped) grid = std::min(grid, ctx->max_grid);
+    if (pl.run_table) MI_TRY(window_bounds(ctx, A, grid, (int)wgs, &grid, &bounds));
+  } else {
+    // one workgroup per CU and one round (the kernel needs > 64 VGPRs: a second round would only repeat the
+    // prologue); the rows mode of several ranks needs the uniform 512-row partial layout instead
+    constexpr int cap = 256;
+    grid = uniform_grid(ctx, sell_groups(A));
+    if (!ctx->uniform_grid && grid > cap) grid = cap;
+    if (pl.run_table) {
+      // the workgroup budget: what is resident at once (one round), at most kMaxRows partial rows
+      const int occ = std::min(window_occupancy(ctx, p, pl), kWaves / kWinWaves);
+      int wgs = std::min(cap * occ, kMaxRows);
+      // (one-GPU rehearsals of several ranks: the pass waits for its neighbours in its prologue, so -- like the CG
+      // kernels -- it must leave room for their kernels while it does; mi_internal.h mi_ctx::max_grid)
+      if (capped) wgs = std::min(wgs, ctx->max_grid);
+      MI_TRY(window_bounds(ctx, A, wgs, ntiles, &grid, &bounds));
+    }
+  }
+  HaloWaitArg<true> hw_halo;  // a push folded into the kernel that wrote `in`: the pass waits in its prologue
   HaloWaitArg<false> hw_none;
-  MI_TRY(comm_halo_exchange_or_wait(ctx, A, p, in->d, &hw_halo.w));
+  if (pl.exchange) MI_TRY(comm_halo_exchange_or_wait(ctx, A, p, in->d, &hw_halo.w));
   hw_halo.halo_lo = (unsigned)A->halo_lo;  // (computed far columns of a row shard: spmm_core.h load_far)
   hw_halo.halo_hi = (unsigned)A->halo_hi;
   SellView view = sell_view(A);  // after the exchange: it selects the halo buffer the rows landed in
-  if (!recur) {
+  const double *slots = ctx->scalars + SLOT_GRAM;
+  if (pl.gram_reduce) {
     if (rows_mode(ctx)) MI_TRY(comm_allreduce_rows(ctx, ctx->partials2, nsym(p)));
-    if (sharded) MI_TRY(sharded_reduce(ctx, gram_count, nsym(p), slots));
+    if (pl.from_slots) MI_TRY(sharded_reduce(ctx, gram_count, nsym(p), ctx->scalars + SLOT_GRAM));
   }
+  const bool fused = pl.form == ST_HESS_PLAIN || pl.form == ST_HESS_WINDOW;
+  WinView wv{A->wk, A->wfar, pl.wc, 2 * kWinWaves + 2 * pl.wc, A->win_zero, bounds,
+             pl.fard ? (unsigned)A->win_far_pure : 0u, fused ? A->wk16 : nullptr};
+  const CgState *live = ctx->cg_live;
+  const double *V = in->d, *X = q->X->d, *Y = q->Y->d, *S = q->S_dev, *gram = ctx->partials2,
+               *gdir = ctx->scalars + SLOT_GDIR, *rres = pl.twok ? ctx->twok_r : nullptr;
+  double *outp = out->d, *parts = ctx->partials;
+  void *hwait = pl.halo ? (void *)&hw_halo : (void *)&hw_none;
+  // the three kernel signatures
+  void *a_fused[] = {&view, &wv, &live, &V, &X, &Y, &S, &gram, &gram_count, &slots, &gdir, &outp, &parts, hwait, &rres};
+  void *a_widewin[] = {&view, &wv, &live, &V, &X, &Y, &S, &gdir, &outp, &parts};
+  void *a_wide[] = {&view, &live, &V, &X, &Y, &S, &gdir, &outp, &parts, hwait, &bounds};
+  void **args = fused ? a_fused : pl.form == ST_HESS_WIDEWIN ? a_widewin : a_wide;
   KScope ks(ctx, MI_K_STIEFEL_HESS_FUSED);
-#define HF3(F, HL, RC, PKV, HWV)                                                                              \
-  DISPATCH_P4(p, hipLaunchKernelGGL((k_st_hess_fused<P, F, HL, RC, PKV, HWV>), dim3(grid), dim3(block), 0,     \
-                                   ctx->stream, view, wv, (const CgState *)ctx->cg_live,                     \
-                                   (const double *)in->d, (const double *)q->X->d, (const double *)q->Y->d,  \
-                                   (const double *)q->S_dev, (const double *)ctx->partials2, gram_count,     \
-                                   (const double *)slots, (const double *)(ctx->scalars + SLOT_GDIR),        \
-                                   out->d, ctx->partials, HW_ARG_##HL))
-#define HW_ARG_true hw_halo
-#define HW_ARG_false hw_none
-#define HF(F, HL, RC)                                                          \
-  if (A->pk) { HF3(F, HL, RC, true, 0); }                                      \
-  else { HF3(F, HL, RC, false, 0); }
-#define HF3D(HWV, FARV)                                                                                       \
-  DISPATCH_P4(p, hipLaunchKernelGGL((k_st_hess_fused<P, false, false, true, true, HWV, FARV>), dim3(grid),      \
-                                   dim3(block), 0, ctx->stream, view, wv, (const CgState *)ctx->cg_live,      \
-                                   (const double *)in->d, (const double *)q->X->d, (const double *)q->Y->d,   \
-                                   (const double *)q->S_dev, (const double *)ctx->partials2, gram_count,      \
-                                   (const double *)slots, (const double *)(ctx->scalars + SLOT_GDIR),         \
-                                   out->d, ctx->partials, hw_none))
-#define HF3DH(HWV)                                                                                            \
-  DISPATCH_P4(p, hipLaunchKernelGGL((k_st_hess_fused<P, false, true, true, true, HWV, 1>), dim3(grid),         \
-                                   dim3(block), 0, ctx->stream, view, wv, (const CgState *)ctx->cg_live,      \
-                                   (const double *)in->d, (const double *)q->X->d, (const double *)q->Y->d,   \
-                                   (const double *)q->S_dev, (const double *)ctx->partials2, gram_count,      \
-                                   (const double *)slots, (const double *)(ctx->scalars + SLOT_GDIR),         \
-                                   out->d, ctx->partials, hw_halo))
-  if (gram_count == -2) {  // the two-kernel step (opt-in experiment): stpcg.hip asked for it only where twok says it exists
-    MI_REQUIRE(win && fard && !halo && !w16 && p == 3 && ctx->twok_r, "internal: two-kernel step without its Hessian form");
-#define HF2K(HWV)                                                                                                       \
-  hipLaunchKernelGGL((k_st_hess_fused<3, false, false, true, true, HWV, 1, true>), dim3(grid), dim3(block), 0,          \
-                     ctx->stream, view, wv, (const CgState *)ctx->cg_live, (const double *)in->d,                       \
-                     (const double *)q->X->d, (const double *)q->Y->d, (const double *)q->S_dev,                        \
-                     (const double *)ctx->partials2, gram_count, (const double *)slots,                                 \
-                     (const double *)(ctx->scalars + SLOT_GDIR), out->d, ctx->partials, hw_none, ctx->twok_r)
-    if (A->win_head <= 7) { HF2K(7); } else { HF2K(8); }
-#undef HF2K
-  } else if (win && w16) {  // the window form with computed far columns and 16-bit words
-    if (A->win_head <= 7) { HF3D(7, 2); } else { HF3D(8, 2); }
-  } else if (win && fard && halo) {  // ... with computed far columns, some of them halo columns
-    if (A->win_head <= 7) { HF3DH(7); } else { HF3DH(8); }
-  } else if (win && fard) {  // ... with computed far columns
-    if (A->win_head <= 7) { HF3D(7, 1); } else { HF3D(8, 1); }
-  } else if (win) {  // the window form (recurrence form only: the unpreconditioned solve)
-    if (A->win_head <= 7) {
-      if (halo) { HF3(false, true, true, true, 7); } else { HF3(false, false, true, true, 7); }
-    } else {
-      if (halo) { HF3(false, true, true, true, 8); } else { HF3(false, false, true, true, 8); }
-    }
-  } else if (recur) {
-    if (halo) { HF(false, true, true); } else { HF(false, false, true); }
-  } else if (halo) {
-    if (sharded) { HF(true, true, false); } else { HF(false, true, false); }
-  } else {
-    if (sharded) { HF(true, false, false); } else { HF(false, false, false); }
-  }
-#undef HF3DH
-#undef HF3D
-#undef HF3
-#undef HF
-#undef HW_ARG_true
-#undef HW_ARG_false
+  MI_HIP(hipLaunchKernel(fn, dim3(grid), dim3(pl.block), args, pl.lds_bytes, ctx->stream));
   *nparts = grid;
   MI_HIP(hipGetLastError());
   return MI_OK;
@@ -1585,6 +1572,20 @@ __attribute__((visibility("default"))) int mi_debug_stamp_buffer(void *dev_ptr) 
   return MI_OK;
 }
 #endif
+
+// Host-only: the launch plan of the one-pass Hessian (st_hess_plan) for plain numbers -- see include/mi355opt.h
+int mi_debug_stiefel_hess_form(int p, int gram_count, const size_t m[9], const int s[9], int out[14]) {
+  MI_REQUIRE(m && s && out, "null argument");
+  const StHessTraits t{m[0] != 0, m[1] != 0, m[2] != 0, (int)m[3], (int)m[4], m[5], m[6], m[7] != 0, m[8] != 0,
+                       s[0] != 0, s[1] != 0, s[2] != 0, s[5] != 0, s[6] != 0, s[7] != 0, s[8] != 0, s[3], s[4]};
+  StHessPlan pl;
+  const int st = st_hess_plan(p, gram_count, t, &pl);
+  if (st != MI_OK) set_error("%s", pl.error);
+  const int v[14] = {pl.form, pl.from_slots, pl.halo, pl.recur, pl.pk, pl.hw, pl.far, pl.twok, pl.block, (int)pl.lds_bytes,
+                     pl.run_table, pl.exchange, pl.gram_reduce, st_hess_twok_exists(p, t)};
+  std::copy(v, v + 14, out);
+  return st;
+}
 
 int mi_stiefel_gram(mi_ctx *ctx, size_t n, int p, const mi_vec *X, const mi_vec *Z, double *G_host) {
   MI_TRY(check_np(ctx, n, p, X, Z, nullptr));
@@ -1718,9 +1719,7 @@ int mi_stiefel_rq_model(mi_stiefel_rq *q, const mi_vec *X, mi_vec *grad, mi_op *
   q->dg.S = q->S_dev;
   q->dg.halo_A = q->A->halo ? q->A : nullptr;
   // (the opt-in two-kernel step: p = 3, window form with computed far columns, one rank)
-  q->dg.twok = q->p == 3 && !q->A->halo && q->A->wk && q->A->win_chunks > 0 && q->A->win_far_pure > 0 &&
-               q->A->win_far_pure < ((size_t)1 << 31) && !q->ctx->cfg.no_window && !q->ctx->cfg.no_far_computed &&
-               !q->ctx->uniform_grid && !(q->A->wk16 && q->ctx->cfg.words16);
+  q->dg.twok = st_hess_twok_exists(q->p, st_hess_traits(q->ctx, q->A));
   // the one-pass kernel uses 32-bit byte offsets: fields of 4 GiB or more keep the two-pass operator -- and so does
   // a matrix that is not symmetric (checked at creation): the one-pass form replaces X'(A p) by (A X)'p
   q->hess.dirgram = (sell_stream_ok(q->A, q->p) && q->A->symmetric) ? &q->dg : nullptr;
