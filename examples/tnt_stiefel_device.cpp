@@ -75,6 +75,26 @@ int main(int argc, char **argv) {
         std::optional<Riemannian::LinearOperator<DeviceVector, DeviceVector>>(), params);
     size_t inner = 0;
     for (size_t k : result.inner_iterations) inner += k;
+    // The same call the way the reference's clients make it, with an extra argument behind x0 (Args = {size_t}: a counter
+    // of ours that our user function increments).  The pack-templated accessors hand out the same tagged callables in
+    // that signature, so the run keeps the fused inner solve and trial step -- and gives the same bits.
+    size_t visits = 0;
+    std::optional<Riemannian::TNTUserFunction<DeviceVector, DeviceVector, double, size_t>> count =
+        Riemannian::TNTUserFunction<DeviceVector, DeviceVector, double, size_t>(
+            [](size_t, double, const DeviceVector &, double, const DeviceVector &,
+               const Riemannian::LinearOperator<DeviceVector, DeviceVector, size_t> &, double, size_t, const DeviceVector &,
+               double, double, bool, size_t &seen) {
+              ++seen;
+              return false;
+            });
+    auto again = Riemannian::TNT<DeviceVector, DeviceVector, double, size_t>(
+        prob.objective<size_t>(), prob.quadratic_model<size_t>(), prob.metric<size_t>(), prob.retraction<size_t>(), x0,
+        visits, std::optional<Riemannian::LinearOperator<DeviceVector, DeviceVector, size_t>>(), params, count);
+    mi_fusion_counters fc;
+    MI355::check(mi_ctx_fusion_counters(ctx.get(), &fc));
+    std::printf("with Args = {size_t}: f differs by %.1e, user function called %zu times, generic inner solves %llu\n",
+                std::fabs(again.f - result.f), visits, (unsigned long long)fc.generic_stpcg_solves);
+    if (again.f != result.f || visits != again.inner_iterations.size() || fc.generic_stpcg_solves != 0) return 3;
     // sum of the p smallest eigenvalues of the grid operator, for comparison
     double exact = 0;
     const int modes[3][3] = {{1, 1, 1}, {1, 1, 2}, {1, 2, 1}};

@@ -362,8 +362,8 @@ MI_API int mi_stpcg_collect(mi_ctx *ctx, mi_stpcg_result *result);
 /* ---------------------------------------------------------------------------------------------
  * (5b) fused LSQR  <->  LinearAlgebra::LSQR  IterativeSolvers.h:552-855 (Paige & Saunders, damped,
  *      with the trust-region radius of :779-793 and the stopping rules S1-S4 of :825-837; the user
- *      function S5 is only available through the generic template loop).  Device-resident like
- *      mi_stpcg: no scalar reaches the host inside the loop.  A: n_x -> n_y, At: n_y -> n_x.
+ *      function S5 through mi_lsqr_observed).  Device-resident like mi_stpcg: no scalar reaches the
+ *      host inside the loop of mi_lsqr.  A: n_x -> n_y, At: n_y -> n_x.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mi_lsqr_params {
   size_t max_iterations; /* :558 (1000) */
@@ -379,7 +379,8 @@ enum {
   MI_LSQR_EXIT_S2 = 2,      /* :829 */
   MI_LSQR_EXIT_S3 = 3,      /* :833 */
   MI_LSQR_EXIT_S4 = 4,      /* :837 */
-  MI_LSQR_EXIT_TRIVIAL = 5  /* A'b = 0: x = 0 returned before the loop (:671-674) */
+  MI_LSQR_EXIT_TRIVIAL = 5, /* A'b = 0: x = 0 returned before the loop (:671-674) */
+  MI_LSQR_EXIT_USER = 6     /* :845-851, the observer of mi_lsqr_observed said stop */
 };
 typedef struct mi_lsqr_result {
   double xnorm;          /* :769-770,793 */
@@ -391,6 +392,38 @@ typedef struct mi_lsqr_result {
 MI_API void mi_lsqr_default_params(mi_lsqr_params *p);
 MI_API int mi_lsqr(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, const mi_lsqr_params *params,
                    mi_vec *x_out, mi_lsqr_result *result); /* sync at exit */
+/* The same solve with the reference's LSQRUserFunction (IterativeSolvers.h:450-456) as a C callback.  The observer is
+ * called at the end of every pass, all quantities updated, behind the stopping rules S1-S4 (:825-851): with x after this
+ * pass's update, the loop index k of the pass (0, 1, ...) and |x|, |rbar|, |Abar' rbar|, the |Abar| and cond(Abar)
+ * estimates.  Not in a pass that leaves through S1-S4, as in the reference; the pass that reaches max_iterations without
+ * a stopping rule is observed (the reference's loop body completes before its `for` condition fails).  x is a read-only
+ * view owned by the solve (x_out itself), valid for the duration of the call.  A non-zero return stops the solve like
+ * the reference's `break` (:849-851): x_out keeps this pass's update, num_iterations = k (not advanced, also when the
+ * pass was the last one allowed), exit_reason = MI_LSQR_EXIT_USER.
+ *   Contract.  The observer runs on the calling thread with the stream drained up to this pass's k_lsqr_xw.  On the same
+ * context it may call the read-only vector functions on the view (mi_vec_dot, mi_vec_dot_batch, mi_vec_download,
+ * mi_vec_copy FROM the view) and the plain applications mi_op_apply(A or At, vector, own vector) -- e.g. for the true
+ * residual b - A x.  It must not write or destroy the view and must not call anything else that computes on that
+ * context: mi_lsqr / mi_lsqr_observed are refused with MI_ERR_INVALID_ARGUMENT; mi_stpcg, the LOBPCG building blocks, the
+ * *_model / *_trial chains and everything built on them are NOT checked and share the reduction buffers with the running
+ * solve.  A C++ exception must not leave it.
+ *   What runs.  The kernels of mi_lsqr (k_lsqr_u, _unorm, _v, _vnorm, _xw, the fused-SpMV forms of the built-in CSR
+ * operators) and the same bits: with an observer that never stops, x_out and the result equal mi_lsqr's.  What differs:
+ * no run-ahead (run_ahead is ignored).  Behind k_lsqr_xw of every pass a one-wave kernel copies the state's
+ * {mode, exit_reason, k, xnorm, rbar_norm, Arnorm, Anorm, Acond} into pinned host words and releases the polled flag: one
+ * small kernel and one polled wait per pass (mi_ctx_sync_count rises by one per pass).  operator_applications is exact
+ * for an observed solve: 1 + 2 * (passes enqueued), nothing speculative -- passes = num_iterations at a MAXIT exit,
+ * num_iterations + 1 where S1-S4 or the observer ended the pass (mi_lsqr's count includes its run-ahead and depends on
+ * timing).
+ *   Returns MI_DECLINED -- nothing done, nothing counted -- on a context that is one of several ranks or completes its
+ * reductions through an exchange layer, with MI355OPT_FORCE_LOCKSTEP, and with MI355OPT_NO_FUSED_LSQR_OBSERVER=1 (the A/B
+ * switch of the template layer): the caller keeps its generic loop. */
+/* the small query behind that: MI_OK, or MI_DECLINED with *why (nullable) pointing at a literal that names the cause */
+MI_API int mi_lsqr_observer_available(mi_ctx *ctx, const char **why);
+typedef int (*mi_lsqr_observer)(void *user, size_t k, const mi_vec *x, double xnorm, double rbar_norm, double Arnorm,
+                                double Anorm, double Acond);
+MI_API int mi_lsqr_observed(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, const mi_lsqr_params *params,
+                            mi_lsqr_observer fn, void *user, mi_vec *x_out, mi_lsqr_result *result);
 
 
 /* ---------------------------------------------------------------------------------------------

@@ -138,7 +138,9 @@ def build_harness(force=False):
       tests/cpp/libharness_host.so    templates on a host vector, same driver code as the real
                                       reference build (oracle/template_driver.inc)
       tests/cpp/libharness_device.so  templates on MI355::DeviceVector, linked to libmi355opt.so
-      tests/cpp/libharness_observer.so  STPCG with a user function on both vector types (one driver)"""
+      tests/cpp/libharness_observer.so  STPCG with a user function on both vector types (one driver)
+      tests/cpp/libharness_args.so    the optimizers called with an extra-argument pack (Args...), empty and not
+      tests/cpp/libharness_lsqr_observer.so  LSQR with a user function: C ABI and template layer"""
     tdir = os.path.join(ROOT, "tests", "cpp")
     inc = ["-I", os.path.join(HERE, "include"), "-I", os.path.join(ROOT, "oracle")]
     common = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-type-limits"]
@@ -180,6 +182,25 @@ def build_harness(force=False):
         if r.returncode != 0:
             raise RuntimeError("observer harness build failed:\n" + r.stderr[-6000:])
     out.append(ob_so)
+    # tests/cpp/harness_args.cpp, harness_lsqr_observer.cpp: g++, and clang's front end on the same translation units
+    # (the pack-carrying instantiations of the template layer must pass both)
+    for name in ("harness_args", "harness_lsqr_observer"):
+        src = os.path.join(tdir, name + ".cpp")
+        so = os.path.join(tdir, "lib" + name + ".so")
+        if force or _newer(src, so, hdrs + [LIB]):
+            # clang first: a translation unit that fails its front end leaves no fresh .so behind to hide that
+            clang = "/opt/rocm/lib/llvm/bin/clang++"
+            if os.path.exists(clang):
+                r = subprocess.run([clang, "-std=c++17", "-fsyntax-only"] + inc +
+                                   ["-I", os.path.join(ROOT, "include"), src], capture_output=True, text=True)
+                if r.returncode != 0:
+                    raise RuntimeError(f"clang front-end check of {name} failed:\n" + r.stderr[-6000:])
+            cmd = common + inc + ["-I", os.path.join(ROOT, "include"), src, "-o", so, "-L", HERE,
+                                  "-lmi355opt", "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib"]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"{name} build failed:\n" + r.stderr[-6000:])
+        out.append(so)
     # tests/cpp/harness_sinfit.hip: the reference's TNLS sin-fit problem with HIP kernels of its own (hipcc)
     sf_src = os.path.join(tdir, "harness_sinfit.hip")
     sf_so = os.path.join(tdir, "libharness_sinfit.so")

@@ -31,6 +31,8 @@ vp = C.c_void_p
 APPLY_FN = C.CFUNCTYPE(C.c_int, vp, vp, vp)
 # mi_stpcg_observer: (user, k, s, r, v, p, alpha) -> nonzero stops the solve
 OBSERVER_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, vp, vp, vp, C.c_double)
+# mi_lsqr_observer: (user, k, x, xnorm, rbar_norm, Arnorm, Anorm, Acond) -> nonzero stops the solve
+LSQR_OBSERVER_FN = C.CFUNCTYPE(C.c_int, vp, C.c_size_t, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double)
 
 
 class PanelBlocks(C.Structure):
@@ -178,6 +180,8 @@ def load():
         "mi_stpcg_observed": [vp, vp, vp, vp, C.POINTER(StpcgParams), OBSERVER_FN, vp, vp, C.POINTER(StpcgResult),
                               C.POINTER(StpcgTrace)],
         "mi_stpcg_observer_available": [vp, C.POINTER(C.c_char_p)],
+        "mi_lsqr_observed": [vp, vp, vp, vp, C.POINTER(LsqrParams), LSQR_OBSERVER_FN, vp, vp, C.POINTER(LsqrResult)],
+        "mi_lsqr_observer_available": [vp, C.POINTER(C.c_char_p)],
         "mi_stiefel_gram": [vp, C.c_size_t, C.c_int, vp, vp, c_double_p],
         "mi_stiefel_project": [vp, C.c_size_t, C.c_int, vp, vp, vp],
         "mi_stiefel_retract": [vp, C.c_size_t, C.c_int, vp, vp, vp],
@@ -579,8 +583,19 @@ class Context:
                     hvp_calls=res.hvp_calls, rv_final=res.rv_final, precon_status=res.precon_status)
 
     # fused LSQR ---------------------------------------------------------------------------------
-    def lsqr(self, A, At, b, x_out=None, **kw):
-        """mi_lsqr: A, At are Op handles (A: n_x -> n_y); kw: max_iterations, lam, btol, Atol, Acond_limit, Delta"""
+    def lsqr_observer_available(self):
+        """mi_lsqr_observer_available: (True, "") or (False, the reason the observed fused solve declines)"""
+        why = C.c_char_p()
+        st = self.L.mi_lsqr_observer_available(self.h, C.byref(why))
+        return st == MI_OK, (why.value or b"").decode()
+
+    def lsqr(self, A, At, b, x_out=None, observer=None, **kw):
+        """mi_lsqr: A, At are Op handles (A: n_x -> n_y); kw: max_iterations, lam, btol, Atol, Acond_limit, Delta
+        observer: callable (k, x, xnorm, rbar_norm, Arnorm, Anorm, Acond) -> bool, the reference's LSQRUserFunction
+        (mi_lsqr_observed): called at the end of every pass that no stopping rule S1-S4 ended, with the loop index of
+        the pass; x is a non-owning Vec wrapper of the solve's own storage, valid for the duration of the call only
+        (read it); a true return stops the solve with x as it is (exit_reason 6, iterations = k).  An exception raised
+        in it stops the solve and is re-raised here after the library call has returned."""
         prm = LsqrParams()
         self.L.mi_lsqr_default_params(C.byref(prm))
         for k, v in kw.items():
@@ -589,7 +604,23 @@ class Context:
             setattr(prm, k, v)
         res = LsqrResult()
         x = x_out if x_out is not None else Vec(self, kw_nx if (kw_nx := getattr(A, "n_in", None)) else b.n)
-        check(self.L.mi_lsqr(self.h, A.h, At.h, b.h, C.byref(prm), x.h, C.byref(res)))
+        if observer is not None:
+            raised = []
+
+            def tramp(_user, k, xh, xnorm, rbar_norm, Arnorm, Anorm, Acond):
+                try:
+                    return 1 if observer(int(k), Vec(self, 0, handle=vp(xh)), float(xnorm), float(rbar_norm),
+                                         float(Arnorm), float(Anorm), float(Acond)) else 0
+                except BaseException as e:  # noqa: nothing may propagate through the C frames
+                    raised.append(e)
+                    return 1
+            cfn = LSQR_OBSERVER_FN(tramp)
+            st = self.L.mi_lsqr_observed(self.h, A.h, At.h, b.h, C.byref(prm), cfn, None, x.h, C.byref(res))
+            if raised:
+                raise raised[0]
+            check(st)
+        else:
+            check(self.L.mi_lsqr(self.h, A.h, At.h, b.h, C.byref(prm), x.h, C.byref(res)))
         return dict(x=x, xnorm=res.xnorm, iterations=res.num_iterations, exit_reason=res.exit_reason,
                     rbar_norm=res.rbar_norm, Arnorm=res.Arnorm, Anorm=res.Anorm, Acond=res.Acond,
                     operator_applications=res.operator_applications)

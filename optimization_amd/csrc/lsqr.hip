@@ -18,6 +18,7 @@
 //   k_lsqr_xw     [both plane rotations, |x| estimate, step lengths, S1-S4] x += t1 w ; w = v + t2 w   :729-837
 // Algorithmic bytes per pass (n_x = n_y = N, operators excluded): 3N + 2N + 3N + 4N + 5N = 17 N * 8.
 #include <cmath>
+#include <cstring>
 #include <utility>
 
 #include "comm_ipc.h"
@@ -384,26 +385,103 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(80))) void k
   }
 }
 
-inline void cpu_relax() { __builtin_ia32_pause(); }
-
-}  // namespace
-
-extern "C" {
-
-void mi_lsqr_default_params(mi_lsqr_params *p) {
-  if (!p) return;
-  p->max_iterations = 1000;  // :558
-  p->lambda = 0;
-  p->btol = 1e-6;
-  p->Atol = 1e-6;
-  p->Acond_limit = 1e8;
-  p->Delta = std::sqrt(1.7976931348623157e308);  // sqrt(numeric_limits<double>::max())  :559
-  p->run_ahead = 3;
+// OBSERVED SOLVE (mi_lsqr_observed): the reference's user function (IterativeSolvers.h:450-456) is called at the end of a
+// pass, every quantity updated, behind the stopping rules S1-S4 (:825-851).  In the fused pass that is the moment behind
+// k_lsqr_xw.  k_lsqr_peek (one wave) hands the state k_lsqr_xw just wrote to the host:
+//   {mode, exit_reason, k, xnorm, rbar_norm, Arnorm, Anorm, Acond}
+// into pinned host words, the context's polled flag behind them.  The state is not written: the kernels of the pass,
+// and the un-observed solve, are untouched.
+__global__ void k_lsqr_peek(const LsqrState *__restrict__ s, unsigned long long *host, unsigned long long *flag,
+                            unsigned long long seq) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  host[0] = (unsigned long long)s->mode;
+  host[1] = (unsigned long long)s->exit_reason;
+  host[2] = s->k;
+  double *hd = reinterpret_cast<double *>(host);
+  hd[3] = s->xnorm;
+  hd[4] = s->rbar_norm;
+  hd[5] = s->Arnorm;
+  hd[6] = s->Anorm;
+  hd[7] = s->Acond;
+  __threadfence_system();
+  if (flag) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-int mi_lsqr(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, const mi_lsqr_params *prm, mi_vec *x_out,
-            mi_lsqr_result *result) {
+// the observer said stop: the reference's `break` at :849-851 -- x keeps this pass's update, and the loop index is that
+// of the interrupted pass (not advanced, :696), also when that pass was the last one allowed.  One thread, in place: no
+// kernel of the solve is in flight beside it.
+__global__ void k_lsqr_user_stop(LsqrState *s, unsigned long long k, HostStatus *hs) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  s->k = k;
+  s->exit_reason = MI_LSQR_EXIT_USER;
+  s->mode = LSQR_DONE;
+  publish(hs, s->launches, 1);
+}
+
+inline void cpu_relax() { __builtin_ia32_pause(); }
+
+// Observed solve, behind k_lsqr_xw of loop index k: the state to the host (one small kernel and one polled wait), then
+// the reference's order (:825-851).  *leave: enqueue nothing more.
+int lsqr_observe(mi_ctx *ctx, LsqrState *s, size_t k, const mi_vec *x, mi_lsqr_observer fn, void *user, bool *leave) {
+  hipStream_t stq = ctx->stream;
+  void *host = nullptr, *dev = nullptr;
+  MI_TRY(readback_area(ctx, 8 * sizeof(unsigned long long), &host, &dev));
+  ctx->host_syncs++;
+  unsigned long long *flag = nullptr;
+  const unsigned long long seq = poll_begin(ctx, &flag);
+  hipLaunchKernelGGL(k_lsqr_peek, dim3(1), dim3(64), 0, stq, (const LsqrState *)s, (unsigned long long *)dev,
+                     seq ? flag : (unsigned long long *)nullptr, seq);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "lsqr observer peek launch", __FILE__, __LINE__);
+  MI_TRY(poll_finish(ctx, seq, "lsqr observer peek"));
+  const volatile unsigned long long *pk = static_cast<const volatile unsigned long long *>(host);
+  const int mode = (int)pk[0], exit_reason = (int)pk[1];
+  const unsigned long long kdev = pk[2];
+  double sc[5];
+  for (int i = 0; i < 5; ++i) {
+    const unsigned long long bits = pk[3 + i];
+    memcpy(&sc[i], &bits, sizeof(double));
+  }
+  // a pass that left through S1-S4 (k not advanced), or a solve that was over before this pass (A'b = 0): no call.
+  // The pass that reached max_iterations without a stopping rule is observed: the reference's loop body completes
+  // before its `for` condition fails.
+  const bool done = mode != LSQR_RUN;
+  *leave = done;
+  if (done && !(exit_reason == MI_LSQR_EXIT_MAXIT && kdev == (unsigned long long)k + 1)) return MI_OK;
+  ctx->lsqr_in_observer = true;
+  const int stop = fn(user, k, x, sc[0], sc[1], sc[2], sc[3], sc[4]);
+  ctx->lsqr_in_observer = false;
+  if (!stop) return MI_OK;
+  *leave = true;
+  hipLaunchKernelGGL(k_lsqr_user_stop, dim3(1), dim3(64), 0, stq, s, (unsigned long long)k, ctx->status_dev);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "lsqr observer stop launch", __FILE__, __LINE__);
+  return MI_OK;
+}
+
+// why the observed solve does not take this context as it is configured (a literal), or nullptr
+const char *lsqr_observer_declines(const mi_ctx *ctx) {
+  if (ctx->cfg.no_fused_lsqr_observer) return "MI355OPT_NO_FUSED_LSQR_OBSERVER is set";
+  if (ctx->world_size > 1) return "the context is one of several ranks";
+  if (ctx->force_lockstep) return "MI355OPT_FORCE_LOCKSTEP is set";
+  if (comm_ipc_enabled(ctx) || slot_mode(ctx) || rows_mode(ctx))
+    return "the context completes its reductions through an exchange layer";
+  return nullptr;
+}
+
+// mi_lsqr (fn == nullptr) and mi_lsqr_observed share this body; the former enqueues exactly what it always did
+int lsqr_solve(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, const mi_lsqr_params *prm, mi_lsqr_observer fn,
+               void *user, mi_vec *x_out, mi_lsqr_result *result) {
   MI_REQUIRE(ctx && A && At && b && prm && x_out && result, "null argument");
+  MI_REQUIRE(!ctx->lsqr_in_observer, "a solve was started on this context from inside an LSQR observer");
+  const bool observed = fn != nullptr;
+  if (observed) {
+    // nothing has been touched or counted yet: the caller keeps its own loop
+    if (const char *why = lsqr_observer_declines(ctx)) {
+      set_error("mi_lsqr_observed declined: %s", why);
+      return MI_DECLINED;
+    }
+  }
   touch(x_out);
   ctx->fusion.fused_lsqr_solves++;
   RangeScope range("mi_lsqr");
@@ -491,7 +569,7 @@ int mi_lsqr(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, const mi_lsqr_par
   // --- passes: speculative enqueue with bounded run-ahead --------------------------------------------
   for (size_t k = 0; k < prm->max_iterations; ++k) {
     uint64_t wd = ctx->status->word;
-    while (!(wd & 1) && k > (wd >> 1) + (uint64_t)run_ahead) {
+    while (!observed && !(wd & 1) && k > (wd >> 1) + (uint64_t)run_ahead) {  // (an observed solve never runs ahead)
       cpu_relax();
       wd = ctx->status->word;
     }
@@ -540,6 +618,11 @@ int mi_lsqr(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, const mi_lsqr_par
                          (const double *)p3, gx, (const double *)v->d, w->d, x_out->d, ctx->status_dev, NoFold{});
     }
     std::swap(sa, sb);
+    if (observed) {
+      bool leave = false;
+      LQ_CHECK(lsqr_observe(ctx, sa, k, x_out, fn, user, &leave));
+      if (leave) break;
+    }
   }
   {
     LsqrState h;
@@ -574,6 +657,39 @@ cleanup:
   mi_vec_destroy(tx);
   pool_free(ctx, sraw);
   return ret;
+}
+
+}  // namespace
+
+extern "C" {
+
+void mi_lsqr_default_params(mi_lsqr_params *p) {
+  if (!p) return;
+  p->max_iterations = 1000;  // :558
+  p->lambda = 0;
+  p->btol = 1e-6;
+  p->Atol = 1e-6;
+  p->Acond_limit = 1e8;
+  p->Delta = std::sqrt(1.7976931348623157e308);  // sqrt(numeric_limits<double>::max())  :559
+  p->run_ahead = 3;
+}
+
+int mi_lsqr(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, const mi_lsqr_params *prm, mi_vec *x_out,
+            mi_lsqr_result *result) {
+  return lsqr_solve(ctx, A, At, b, prm, nullptr, nullptr, x_out, result);
+}
+
+int mi_lsqr_observer_available(mi_ctx *ctx, const char **why) {
+  MI_REQUIRE(ctx, "null argument");
+  const char *w = lsqr_observer_declines(ctx);
+  if (why) *why = w ? w : "";
+  return w ? MI_DECLINED : MI_OK;
+}
+
+int mi_lsqr_observed(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, const mi_lsqr_params *prm, mi_lsqr_observer fn,
+                     void *user, mi_vec *x_out, mi_lsqr_result *result) {
+  MI_REQUIRE(fn, "mi_lsqr_observed: null observer (mi_lsqr is the solve without one)");
+  return lsqr_solve(ctx, A, At, b, prm, fn, user, x_out, result);
 }
 
 }  // extern "C"

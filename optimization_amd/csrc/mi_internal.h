@@ -178,6 +178,8 @@ struct Config {
                                     // (k_cg_pupdate_ds; same bits, 4.5 N instead of 5 N doubles per iteration); 0: every iteration
   bool no_fused_observer = false;   // NO_FUSED_OBSERVER: mi_stpcg_observed declines (MI_DECLINED) and STPCG with a user function on
                                     // MI355::DeviceVector runs the generic loop, one kernel per vector statement (A/B)
+  bool no_fused_lsqr_observer = false;  // NO_FUSED_LSQR_OBSERVER: mi_lsqr_observed declines (MI_DECLINED) and LSQR with a user function
+                                    // on MI355::DeviceVector runs the generic loop (A/B)
   bool so3_no_rquat = false;        // SO3_NO_RQUAT: the SO(3)^N model assembly gathers the neighbours' rotations as 72-byte matrices
                                     // (r05 form) instead of 32-byte quaternions written by the retraction (r06; creation-time)
   bool so3_no_quat = false;         // SO3_NO_QUAT: the measurements of mi_so3n stay 3 x 3 matrices (r04 form; creation-time)
@@ -225,6 +227,7 @@ struct mi_ctx {
   bool cg_deferred = false;
   size_t cg_deferred_hvp = 0;
   bool cg_in_observer = false;      // mi_stpcg_observed is inside its observer: no solve may start on this context
+  bool lsqr_in_observer = false;    // the same for mi_lsqr_observed
   unsigned long long cg_deferred_seq = 0;  // polled form of the deferred result (0: the event form)
   mi::HostStatus *status = nullptr;      // pinned, device-visible
   mi::HostStatus *status_dev = nullptr;  // device pointer of the same memory

@@ -13,8 +13,10 @@
 // to the fused HIP implementation (mi_stpcg: 4 streaming kernels per iteration, device-resident
 // scalars, no host read-back inside the loop).  A user function keeps that loop (mi_stpcg_observed:
 // the same kernels, plus one small kernel and one polled wait per pass that bring alpha_k to the host;
-// context switch NO_FUSED_OBSERVER restores the generic loop).  Every other combination runs the
-// generic loop below through the Vector's operators.
+// context switch NO_FUSED_OBSERVER restores the generic loop); LSQR likewise (mi_lsqr, mi_lsqr_observed,
+// NO_FUSED_LSQR_OBSERVER).  An Args... pack does not matter to either: the tagged callables ignore it,
+// a user function receives it.  Every other combination runs the generic loop below through the
+// Vector's operators.
 #pragma once
 
 #include <algorithm>
@@ -57,6 +59,17 @@ using STPCGUserFunction = std::function<bool(
 template <typename Vector, typename Multiplier, typename... Args>
 using STPCGPreconditioner = LinearOperator<Vector, std::pair<Vector, Multiplier>, Args...>;
 
+// Observer invoked at the end of every LSQR pass (all quantities already updated); returning true
+// stops the solver.                                                              (reference :450-456)
+// On MI355::DeviceVector with the tagged callables xk is a view of the fused solver's own storage, valid during the
+// call: read it (dot, to_host, copy), do not write it, and do not start another solve on the same context from inside.
+template <typename VectorX, typename VectorY, typename Scalar = double, typename... Args>
+using LSQRUserFunction = std::function<bool(
+    size_t k, const LinearOperator<VectorX, VectorY, Args...> &A,
+    const LinearOperator<VectorY, VectorX, Args...> &At, const VectorY &b, const VectorX &xk,
+    Scalar xk_norm, Scalar rbar_norm, Scalar Abar_rbar_norm, Scalar Abar_norm_est, Scalar Abar_cond_est,
+    Args &...args)>;
+
 namespace detail {
 
 // Step to the trust-region boundary along p from s, in the M-norm, from the three running
@@ -75,7 +88,9 @@ bool stpcg_on_device(const Vector &g, const SymmetricLinearOperator<Vector, Args
                      const std::optional<LinearOperator<Multiplier, Vector, Args...>> &At,
                      const std::optional<STPCGUserFunction<Vector, Multiplier, Scalar, Args...>> &user_function,
                      Scalar Delta, size_t max_iterations, Scalar kappa_fgr, Scalar theta, Scalar epsilon,
-                     Vector &s_out, Scalar &update_step_M_norm, size_t &num_iterations, const char *&why) {
+                     Vector &s_out, Scalar &update_step_M_norm, size_t &num_iterations, const char *&why,
+                     Args &...args) {
+  // `args`: the caller's pack, handed on to the user function only (the tagged callables ignore it)
   // `why`: which probe sent the solve to the generic loop (reported through mi_ctx_note_generic by the caller)
   if constexpr (!MI355::is_device_vector<Vector>::value || !std::is_same<Scalar, double>::value) {
     why = "Scalar is not double";
@@ -137,14 +152,16 @@ bool stpcg_on_device(const Vector &g, const SymmetricLinearOperator<Vector, Args
       if (mi_stpcg_observer_available(g.context(), &declined) != MI_OK) return no(declined);
       s_out = DeviceVector::like(g);
       // the user function observes the fused solve (mi_stpcg_observed): the four handles as non-owning DeviceVectors,
-      // the caller's own g, H, P, At.  An exception must not cross the C ABI: it stops the solve and is rethrown here,
-      // after the library has read back and cleaned up.
+      // the caller's own g, H, P, At and -- as a tuple of references -- the caller's own args... (reference :365-366).
+      // An exception must not cross the C ABI: it stops the solve and is rethrown here, after the library has read back
+      // and cleaned up.
       struct Trampoline {
         const STPCGUserFunction<Vector, Multiplier, Scalar, Args...> &fn;
         const Vector &g;
         const SymmetricLinearOperator<Vector, Args...> &H;
         const std::optional<STPCGPreconditioner<Vector, Multiplier, Args...>> &P;
         const std::optional<LinearOperator<Multiplier, Vector, Args...>> &At;
+        std::tuple<Args &...> args;
         std::exception_ptr thrown;
         static int call(void *user, size_t k, const mi_vec *s, const mi_vec *r, const mi_vec *v, const mi_vec *p,
                         double alpha) {
@@ -155,13 +172,16 @@ bool stpcg_on_device(const Vector &g, const SymmetricLinearOperator<Vector, Args
             const DeviceVector rk = DeviceVector::view(c, const_cast<mi_vec *>(r));
             const DeviceVector vk = DeviceVector::view(c, const_cast<mi_vec *>(v));
             const DeviceVector pk = DeviceVector::view(c, const_cast<mi_vec *>(p));
-            return t.fn(k, t.g, t.H, t.P, t.At, sk, rk, vk, pk, alpha) ? 1 : 0;
+            return std::apply(
+                       [&](Args &...a) { return t.fn(k, t.g, t.H, t.P, t.At, sk, rk, vk, pk, alpha, a...); }, t.args)
+                       ? 1
+                       : 0;
           } catch (...) {
             t.thrown = std::current_exception();
             return 1;
           }
         }
-      } tramp{*user_function, g, H, P, At, nullptr};
+      } tramp{*user_function, g, H, P, At, std::tuple<Args &...>(args...), nullptr};
       prm.defer_result = 0;
       const int st = mi_stpcg_observed(g.context(), g.handle(), dop->op, prec, &prm, &Trampoline::call, &tramp,
                                        s_out.handle(), &res, nullptr);
@@ -180,17 +200,21 @@ bool stpcg_on_device(const Vector &g, const SymmetricLinearOperator<Vector, Args
   }
 }
 
-// Fused device LSQR (mi_lsqr): both operators tagged DeviceOperator, both inner products Frobenius.
+// Fused device LSQR (mi_lsqr): both operators tagged DeviceOperator, both inner products Frobenius.  A user function
+// observes the fused solve (mi_lsqr_observed: the same kernels, plus one small kernel and one polled wait per pass;
+// context switch NO_FUSED_LSQR_OBSERVER restores the generic loop).  `args`: the caller's pack, handed on to the user
+// function only (the tagged callables ignore it).
 template <typename VectorX, typename VectorY, typename Scalar, typename... Args>
 bool lsqr_on_device(const LinearOperator<VectorX, VectorY, Args...> &A,
                     const LinearOperator<VectorY, VectorX, Args...> &At, const VectorY &b,
                     const InnerProduct<VectorX, Scalar, Args...> &ipx,
                     const InnerProduct<VectorY, Scalar, Args...> &ipy, size_t max_iterations, Scalar lambda,
-                    Scalar btol, Scalar Atol, Scalar Abar_cond_limit, Scalar Delta, VectorX &x_out, Scalar &xnorm,
-                    size_t &num_iterations, const char *&why) {
+                    Scalar btol, Scalar Atol, Scalar Abar_cond_limit, Scalar Delta,
+                    const std::optional<LSQRUserFunction<VectorX, VectorY, Scalar, Args...>> &user_function,
+                    VectorX &x_out, Scalar &xnorm, size_t &num_iterations, const char *&why, Args &...args) {
   if constexpr (!MI355::is_device_vector<VectorX>::value || !MI355::is_device_vector<VectorY>::value ||
-                !std::is_same<Scalar, double>::value || sizeof...(Args) != 0) {
-    why = "extra arguments (Args...), a Scalar other than double, or a host vector type";
+                !std::is_same<Scalar, double>::value) {
+    why = "a Scalar other than double, or a host vector type";
     return false;
   } else {
     using namespace MI355;
@@ -217,8 +241,47 @@ bool lsqr_on_device(const LinearOperator<VectorX, VectorY, Args...> &A,
     prm.Acond_limit = Abar_cond_limit;
     prm.Delta = Delta;
     mi_lsqr_result res;
-    x_out = DeviceVector::on(b.context(), nx);
-    check(mi_lsqr(b.context(), da->op, dat->op, b.handle(), &prm, x_out.handle(), &res));
+    if (user_function) {
+      // (multi-rank / exchange-layer contexts and the A/B switch NO_FUSED_LSQR_OBSERVER: the generic loop, and why)
+      const char *declined = nullptr;
+      if (mi_lsqr_observer_available(b.context(), &declined) != MI_OK) return no(declined);
+      x_out = DeviceVector::on(b.context(), nx);
+      // x as a non-owning DeviceVector, the caller's own A, At, b and -- as a tuple of references -- the caller's own
+      // args... (reference :845-848).  An exception must not cross the C ABI: it stops the solve and is rethrown here,
+      // after the library has read back and cleaned up.
+      struct Trampoline {
+        const LSQRUserFunction<VectorX, VectorY, Scalar, Args...> &fn;
+        const LinearOperator<VectorX, VectorY, Args...> &A;
+        const LinearOperator<VectorY, VectorX, Args...> &At;
+        const VectorY &b;
+        std::tuple<Args &...> args;
+        std::exception_ptr thrown;
+        static int call(void *user, size_t k, const mi_vec *x, double xn, double rbar_norm, double Arnorm, double Anorm,
+                        double Acond) {
+          Trampoline &t = *static_cast<Trampoline *>(user);
+          try {
+            const DeviceVector xk = DeviceVector::view(t.b.context(), const_cast<mi_vec *>(x));
+            return std::apply(
+                       [&](Args &...a) {
+                         return t.fn(k, t.A, t.At, t.b, xk, xn, rbar_norm, Arnorm, Anorm, Acond, a...);
+                       },
+                       t.args)
+                       ? 1
+                       : 0;
+          } catch (...) {
+            t.thrown = std::current_exception();
+            return 1;
+          }
+        }
+      } tramp{*user_function, A, At, b, std::tuple<Args &...>(args...), nullptr};
+      const int st = mi_lsqr_observed(b.context(), da->op, dat->op, b.handle(), &prm, &Trampoline::call, &tramp,
+                                      x_out.handle(), &res);
+      if (tramp.thrown) std::rethrow_exception(tramp.thrown);
+      check(st);
+    } else {
+      x_out = DeviceVector::on(b.context(), nx);
+      check(mi_lsqr(b.context(), da->op, dat->op, b.handle(), &prm, x_out.handle(), &res));
+    }
     xnorm = res.xnorm;
     num_iterations = res.num_iterations;
     return true;
@@ -262,14 +325,12 @@ Vector STPCG(const Vector &g, const SymmetricLinearOperator<Vector, Args...> &H,
 
 #if OPTIMIZATION_HAVE_MI355
   if constexpr (MI355::is_device_vector<Vector>::value) {
-    const char *why = "extra arguments (Args...) are passed to the callables";
-    if constexpr (sizeof...(Args) == 0) {
-      Vector s_dev;
-      if (detail::stpcg_on_device<Vector, Multiplier, Scalar>(g, H, inner_product, P, At, user_function, Delta,
-                                                              max_iterations, kappa_fgr, theta, epsilon, s_dev,
-                                                              update_step_M_norm, num_iterations, why))
-        return s_dev;
-    }
+    const char *why = "";
+    Vector s_dev;
+    if (detail::stpcg_on_device<Vector, Multiplier, Scalar, Args...>(g, H, inner_product, P, At, user_function, Delta,
+                                                                     max_iterations, kappa_fgr, theta, epsilon, s_dev,
+                                                                     update_step_M_norm, num_iterations, why, args...))
+      return s_dev;
     // the generic loop below on device vectors: make the fall observable (mi_ctx_fusion_counters, MI355OPT_WARN_GENERIC)
     if (!g.empty()) (void)mi_ctx_note_generic(g.context(), MI_GENERIC_STPCG, why);
   }
@@ -356,15 +417,6 @@ Vector STPCG(const Vector &g, const SymmetricLinearOperator<Vector, Args...> &H,
   return s;
 }
 
-// Observer invoked at the end of every LSQR pass (all quantities already updated); returning true
-// stops the solver.                                                              (reference :450-456)
-template <typename VectorX, typename VectorY, typename Scalar = double, typename... Args>
-using LSQRUserFunction = std::function<bool(
-    size_t k, const LinearOperator<VectorX, VectorY, Args...> &A,
-    const LinearOperator<VectorY, VectorX, Args...> &At, const VectorY &b, const VectorX &xk,
-    Scalar xk_norm, Scalar rbar_norm, Scalar Abar_rbar_norm, Scalar Abar_norm_est, Scalar Abar_cond_est,
-    Args &...args)>;
-
 // LSQR (Paige & Saunders) for   min_x |A x - b|^2 + lambda |x|^2   s.t. |x| <= Delta,
 // i.e. the damped system Abar = [A; sqrt(lambda) I], bbar = [b; 0], with the stopping rules
 //   S1 |rbar| <= btol |b| + Atol |Abar| |x|,   S2 |Abar' rbar| <= Atol |Abar| |rbar|,
@@ -392,14 +444,13 @@ VectorX LSQR(const LinearOperator<VectorX, VectorY, Args...> &A,
 
 #if OPTIMIZATION_HAVE_MI355
   {
-    const char *why = "a user function is supplied (it observes every iteration's vectors)";
-    if (!user_function) {
-      VectorX x_dev;
-      if (detail::lsqr_on_device<VectorX, VectorY, Scalar, Args...>(A, At, b, inner_product_x, inner_product_y,
-                                                                    max_iterations, lambda, btol, Atol, Abar_cond_limit,
-                                                                    Delta, x_dev, xnorm, num_iterations, why))
-        return x_dev;
-    }
+    const char *why = "";
+    VectorX x_dev;
+    if (detail::lsqr_on_device<VectorX, VectorY, Scalar, Args...>(A, At, b, inner_product_x, inner_product_y,
+                                                                  max_iterations, lambda, btol, Atol, Abar_cond_limit,
+                                                                  Delta, user_function, x_dev, xnorm, num_iterations,
+                                                                  why, args...))
+      return x_dev;
     if constexpr (MI355::is_device_vector<VectorY>::value)
       if (!b.empty()) (void)mi_ctx_note_generic(b.context(), MI_GENERIC_LSQR, why);
   }

@@ -32,7 +32,10 @@ class RotationAveraging {
 
   size_t rotations() const { return N_; }
 
-  Objective<Vector, double> objective() {
+  // (every accessor: `Args...` is the extra-argument pack of the caller's signatures -- prob.objective<Cache>() --
+  // empty by default.  The tagged objects ignore the pack; a lambda wrapped around them would lose the tag.)
+  template <typename... Args>
+  Objective<Vector, double, Args...> objective() {
     return DeviceObjective{this, [this](const Vector &R) {
                              double f = 0;
                              check(mi_so3n_objective(prob_, R.handle(), &f));
@@ -41,18 +44,23 @@ class RotationAveraging {
   }
   // gradient in so(3)^N coordinates + the 3x3-block sparse Hessian assembled at R; also refreshes the
   // block-Jacobi preconditioner returned by preconditioner()
-  Riemannian::QuadraticModel<Vector, Vector> quadratic_model() {
-    return [this](const Vector &R, Vector &grad, Riemannian::LinearOperator<Vector, Vector> &Hess) {
+  template <typename... Args>
+  Riemannian::QuadraticModel<Vector, Vector, Args...> quadratic_model() {
+    return [this](const Vector &R, Vector &grad, Riemannian::LinearOperator<Vector, Vector, Args...> &Hess, Args &...) {
       if (grad.empty() || grad.size() != 3 * N_) grad = Vector(ctx_, 3 * N_);
       mi_op *op = nullptr;
       check(mi_so3n_model(prob_, R.handle(), grad.handle(), &op, &bj_));
       Hess = DeviceHessian{op, this};
     };
   }
-  Riemannian::RiemannianMetric<Vector, Vector, double> metric() { return FrobeniusMetric{}; }
+  template <typename... Args>
+  Riemannian::RiemannianMetric<Vector, Vector, double, Args...> metric() {
+    return FrobeniusMetric{};
+  }
   // R_i exp(hat(xi_i)) -- tagged: TNT evaluates a whole trial step (retraction, f at the trial point, the
   // predicted-decrease terms, the model and both gradient norms at the trial point) through mi_so3n_trial, one read-back
-  Riemannian::Retraction<Vector, Vector> retraction() {
+  template <typename... Args>
+  Riemannian::Retraction<Vector, Vector, Args...> retraction() {
     DeviceTrialRetraction r;
     r.owner = this;
     r.retract = [this](const Vector &R, const Vector &xi) {
@@ -84,7 +92,8 @@ class RotationAveraging {
     };
   }
   // 3x3 block-Jacobi; valid after the first quadratic_model() call (TNT calls QM before precon)
-  Riemannian::LinearOperator<Vector, Vector> preconditioner() {
+  template <typename... Args>
+  Riemannian::LinearOperator<Vector, Vector, Args...> preconditioner() {
     if (!bj_) {
       // bind the (problem-owned) handle now; its inverse blocks are refreshed by every model call
       Vector tmpR(ctx_, 9 * N_), tmpg(ctx_, 3 * N_);

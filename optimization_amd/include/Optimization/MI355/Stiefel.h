@@ -10,6 +10,9 @@
 //       prob.objective(), prob.quadratic_model(), prob.metric(), prob.retraction(), X0,
 //       std::optional<Optimization::Riemannian::LinearOperator<DeviceVector, DeviceVector>>(), params);
 //   (as with the reference, an empty Args pack needs a TYPED empty optional for `precon`)
+// A client whose callables take the reference's extra arguments (`Args &...`, a cache for instance) asks for the same
+// tagged objects in that signature -- prob.objective<Cache>(), prob.quadratic_model<Cache>(), ... -- and keeps the
+// fused paths; wrapping prob.objective() in a lambda of the longer signature would lose the tag.
 #pragma once
 
 #include <cstdint>
@@ -45,7 +48,10 @@ class StiefelRayleighQuotient {
   // f(X) = 1/2 tr(X' A X)
   // (tagged with this object as owner: TNT / GradientDescent fuse the trial step only when objective, model,
   // gradient field and retraction all come from the same problem object -- MI355/Device.h)
-  Objective<Vector, double> objective() {
+  // (every accessor: `Args...` is the extra-argument pack of the caller's signatures; empty by default.  The tagged
+  // objects ignore the pack.)
+  template <typename... Args>
+  Objective<Vector, double, Args...> objective() {
     return DeviceObjective{this, [this](const Vector &X) {
                              double f = 0;
                              check(mi_stiefel_rq_objective(prob_, X.handle(), &f));
@@ -53,18 +59,23 @@ class StiefelRayleighQuotient {
                            }};
   }
   // grad f(X) = A X - X sym(X'AX);  Hess f(X)[V] = P_X(A V - V sym(X'AX)) as a device operator
-  Riemannian::QuadraticModel<Vector, Vector> quadratic_model() {
-    return [this](const Vector &X, Vector &grad, Riemannian::LinearOperator<Vector, Vector> &Hess) {
+  template <typename... Args>
+  Riemannian::QuadraticModel<Vector, Vector, Args...> quadratic_model() {
+    return [this](const Vector &X, Vector &grad, Riemannian::LinearOperator<Vector, Vector, Args...> &Hess, Args &...) {
       if (grad.empty() || grad.size() != n_ * (size_t)p_) grad = Vector(ctx_, n_ * (size_t)p_);
       mi_op *op = nullptr;
       check(mi_stiefel_rq_model(prob_, X.handle(), grad.handle(), &op));
       Hess = DeviceHessian{op, this};
     };
   }
-  Riemannian::RiemannianMetric<Vector, Vector, double> metric() { return FrobeniusMetric{}; }
+  template <typename... Args>
+  Riemannian::RiemannianMetric<Vector, Vector, double, Args...> metric() {
+    return FrobeniusMetric{};
+  }
   // polar retraction (X + V) ((X+V)'(X+V))^-1/2 -- tagged: TNT evaluates a whole trial step (retraction, f at the
   // trial point, the predicted-decrease terms, the next gradient) through mi_stiefel_rq_trial, one read-back
-  Riemannian::Retraction<Vector, Vector> retraction() {
+  template <typename... Args>
+  Riemannian::Retraction<Vector, Vector, Args...> retraction() {
     DeviceTrialRetraction r;
     r.owner = this;
     r.retract = [this](const Vector &X, const Vector &V) {
@@ -97,7 +108,8 @@ class StiefelRayleighQuotient {
     return r;
   }
   // grad f(X) as a VectorField (GradientDescent's interface); after a fused trial at X it is already there
-  Riemannian::VectorField<Vector, Vector> gradient() {
+  template <typename... Args>
+  Riemannian::VectorField<Vector, Vector, Args...> gradient() {
     return DeviceGradientField{this, [this](const Vector &X) {
                                  Vector grad(ctx_, n_ * (size_t)p_);
                                  check(mi_stiefel_rq_model(prob_, X.handle(), grad.handle(), nullptr));

@@ -142,8 +142,7 @@ GradientDescentResult<Variable, Scalar> GradientDescent(
     Scalar trial_grad_sqnorm = 0;
 #if OPTIMIZATION_GD_HAVE_MI355
     const MI355::DeviceTrialRetraction *armijo = nullptr;
-    if constexpr (MI355::is_device_vector<Tangent>::value && MI355::is_device_vector<Variable>::value &&
-                  sizeof...(Args) == 0) {
+    if constexpr (MI355::is_device_vector<Tangent>::value && MI355::is_device_vector<Variable>::value) {
       if (metric.template target<MI355::FrobeniusMetric>()) {
         armijo = retract.template target<MI355::DeviceTrialRetraction>();
         const auto *fo = f.template target<MI355::DeviceObjective>();
@@ -158,8 +157,7 @@ GradientDescentResult<Variable, Scalar> GradientDescent(
       ls_iters++;
       t *= params.beta;
 #if OPTIMIZATION_GD_HAVE_MI355
-      if constexpr (MI355::is_device_vector<Tangent>::value && MI355::is_device_vector<Variable>::value &&
-                    sizeof...(Args) == 0) {
+      if constexpr (MI355::is_device_vector<Tangent>::value && MI355::is_device_vector<Variable>::value) {
         if (armijo) {
           auto a = armijo->armijo(x, g, t);
           h = std::move(a.h);

@@ -178,8 +178,8 @@ TNLS(const Mapping<VariableX, VectorY, Args...> &F, const JacobianPairFunction<V
   // mi_op each, bound to x: MI355::DeviceHessian) and the metric is the Frobenius one, LSQR receives the
   // tagged callables it recognises and the whole inner solve runs in the fused mi_lsqr.  Redone after
   // every linearisation because J may hand back new operators.
-  constexpr bool device_types = MI355::is_device_vector<TangentX>::value &&
-                                MI355::is_device_vector<VectorY>::value && sizeof...(Args) == 0;
+  // (any Args...: the tagged callables ignore the pack)
+  constexpr bool device_types = MI355::is_device_vector<TangentX>::value && MI355::is_device_vector<VectorY>::value;
   // (with a right preconditioner whose two halves are tagged device operators as well, A = dF o M and A' = M' o dF^*
   // (:432-447) are composed on the device -- mi_op_create_compose -- so that the preconditioned solve stays fused too)
   std::shared_ptr<mi_op> composed_A, composed_At;

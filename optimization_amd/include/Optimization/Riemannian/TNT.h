@@ -180,7 +180,7 @@ TNT(const Objective<Variable, Scalar, Args...> &f, const QuadraticModel<Variable
   // Device fast path: swap the generic lambdas for the tagged function objects that STPCG recognises.
   // H and Pop are rebuilt after every QM call because the user's QuadraticModel may hand back a new
   // device operator each time.
-  constexpr bool device_types = MI355::is_device_vector<Tangent>::value && sizeof...(Args) == 0;
+  constexpr bool device_types = MI355::is_device_vector<Tangent>::value;  // (any Args...: the tagged callables ignore the pack)
   auto retag_for_device = [&]() {
     if constexpr (device_types) {
       // back to the generic views first: a QuadraticModel may hand back a tagged device operator at one iterate and
