@@ -614,6 +614,11 @@ MI_API int mi_comm_kernel_launches(mi_ctx *ctx, unsigned long long out[4]);
  * stride D when every entry outside the window is at row +- D (the kernels then compute those columns, halo columns
  * of a row shard included) else 0, halo rows} */
 MI_API int mi_debug_csr_window_info(const mi_csr *A, size_t out[4]);
+/* read-only: what the value-indexed formats of a matrix hold: out = {packed copy (0 / 1), entries of the value table,
+ * index of 0.0 (the one the window words use where there is a window form: the table's size when 0.0 had to be
+ * appended; else its place in the table, SIZE_MAX when it has none), 16-bit window words (0 / 1), the stride in rows
+ * shared by >= 80 % of the entries outside the window or 0} */
+MI_API int mi_debug_csr_format_info(const mi_csr *A, size_t out[5]);
 /* read-only: the forms an SO(3)^N problem took -- {measurements stored as unit quaternions, neighbours gathered as
  * quaternions, slices, incidences, padded incidence slots, workgroups of the model assembly}; needs no GPU work */
 MI_API int mi_debug_so3n_info(const mi_so3n *q, size_t out[6]);

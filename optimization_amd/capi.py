@@ -233,6 +233,7 @@ def load():
         "mi_comm_kernel_launches": [vp, C.POINTER(C.c_ulonglong)],
         "mi_comm_ipc_fold": [vp, C.c_int],
         "mi_debug_csr_window_info": [vp, c_size_p],
+        "mi_debug_csr_format_info": [vp, c_size_p],
         "mi_debug_so3n_info": [vp, c_size_p],
         "mi_debug_time_fused_apply": [vp, vp, vp, C.c_int, c_double_p],
         "mi_debug_set_rank": [vp, C.c_int, C.c_int],
@@ -960,6 +961,13 @@ class Csr:
         out = (C.c_size_t * 4)()
         check(self.L.mi_debug_csr_window_info(self.h, out))
         return tuple(int(v) for v in out)
+
+    def format_info(self):
+        """mi_debug_csr_format_info: dict(packed, ntable, zidx (None: no 0.0 in the table), wk16, far_stride)"""
+        out = (C.c_size_t * 5)()
+        check(self.L.mi_debug_csr_format_info(self.h, out))
+        zidx = None if out[2] == C.c_size_t(-1).value else int(out[2])
+        return dict(packed=bool(out[0]), ntable=int(out[1]), zidx=zidx, wk16=bool(out[3]), far_stride=int(out[4]))
 
     def debug_set_halo(self, p, rows):
         rows = np.ascontiguousarray(rows, dtype=np.float64)

@@ -598,6 +598,7 @@ struct mi_csr {
   uint32_t *pk = nullptr;          // device, padded (null: not representable)
   double *vtab = nullptr;          // device, 256 doubles
   int nvtab = 0;
+  int vtab_zero = -1;              // index of +0.0 in vtab, -1: not among the stored values
   // LDS-window form of the sparse kernels (spmm_core.h sell_window): entries whose column lies within
   // 64 * win_chunks rows of their row are gathered from an LDS ring of the workgroup's rows of V instead of
   // through L1/L2.  0: the matrix does not qualify (decided at creation, sparse.hip build_window).

@@ -426,6 +426,8 @@ int build_sell(mi_ctx *ctx, size_t n, size_t ncols, size_t nnz, const int32_t *r
       MI_TRY(upload((void **)&A->pk, pk.data(), pk.size() * sizeof(uint32_t)));
       MI_TRY(upload((void **)&A->vtab, table.data(), 256 * sizeof(double)));
       A->nvtab = (int)index.size();
+      const auto zero_at = index.find(0);  // (+0.0 by bit pattern)
+      A->vtab_zero = zero_at == index.end() ? -1 : zero_at->second;
       // the window form of the same matrix, when it qualifies (local columns only: col, not pcol)
       MI_TRY(build_window(A, n, nnz, rowptr, col, sp, pk, table, ntable, halo_lo, ncols - n - halo_lo));
     }
@@ -771,6 +773,20 @@ int mi_debug_csr_window_info(const mi_csr *A, size_t out[4]) {
   out[1] = (size_t)A->win_head;
   out[2] = A->win_far_pure;
   out[3] = A->halo_lo + A->halo_hi;
+  return MI_OK;
+}
+
+// Verification hook, read-only: what the value-indexed formats of a matrix hold (tests): out = {packed copy yes / no,
+// entries of the value table, index of 0.0 -- the one the window words use when there is a window form (the table's
+// size when 0.0 was appended for it), else its place in the table, SIZE_MAX when the table has none --, 16-bit window
+// words yes / no, the stride shared by >= 80 % of the far entries or 0}
+int mi_debug_csr_format_info(const mi_csr *A, size_t out[5]) {
+  MI_REQUIRE(A && out, "null argument");
+  out[0] = A->pk != nullptr;
+  out[1] = (size_t)A->nvtab;
+  out[2] = A->wk ? (size_t)(A->win_zero & 255u) : A->vtab_zero >= 0 ? (size_t)A->vtab_zero : SIZE_MAX;
+  out[3] = A->wk16 != nullptr;
+  out[4] = A->win_far_stride;
   return MI_OK;
 }
 
