@@ -177,7 +177,7 @@ MI_API int mi_vec_dot_batch(mi_ctx *ctx, int k, const mi_vec *const *x, const mi
 MI_API int mi_csr_create(mi_ctx *ctx, size_t n, size_t nnz, const int32_t *rowptr,
                          const int32_t *col, const double *val, mi_csr **out); /* sync (upload) */
 MI_API int mi_csr_destroy(mi_csr *A);
-/* W (n x p row-major) = A V ; 1 <= p <= 8 */
+/* W (n x p row-major) = A V ; 1 <= p <= 16 (p = 9 ... 16: one context, not row-sharded) */
 MI_API int mi_csr_spmm(const mi_csr *A, int p, const mi_vec *V, mi_vec *W);
 
 /* ---------------------------------------------------------------------------------------------
@@ -427,11 +427,14 @@ MI_API int mi_lsqr_observed(mi_ctx *ctx, mi_op *A, mi_op *At, const mi_vec *b, c
 
 
 /* ---------------------------------------------------------------------------------------------
- * (6) Stiefel manifold St(n,p), 1 <= p <= 8, embedded metric -- the callables a client of
+ * (6) Stiefel manifold St(n,p), 1 <= p <= 16, embedded metric -- the callables a client of
  *     TNT supplies (Objective, QuadraticModel, RiemannianMetric, Retraction; sphere analogue in
  *     the reference: tests/TNT_unit_test.cpp:73-117).  p <= 4: rows in registers, 1024-thread workgroups, the
  *     LDS-window form of the one-pass Hessian for p <= 3; p = 5 ... 8: the wide-row one-pass Hessian (256-thread
- *     workgroups, the p x p matrices in LDS) in STPCG's recurrence form, the two-pass operator with a preconditioner
+ *     workgroups, the p x p matrices in LDS) in STPCG's recurrence form, the two-pass operator with a preconditioner;
+ *     p = 9 ... 16: the tall-row family (16 x 16 tiles on the fp64 matrix pipe, p a run-time argument): the two-pass
+ *     operator with the curvature dots fused into its finish pass, on ONE context -- with a communicator, a
+ *     row-sharded matrix or MI355OPT_FORCE_SLOT_PATH these widths are refused (MI_ERR_INVALID_ARGUMENT)
  * ------------------------------------------------------------------------------------------- */
 MI_API int mi_stiefel_gram(mi_ctx *ctx, size_t n, int p, const mi_vec *X, const mi_vec *Z,
                            double *G_host /* p*p row-major, sync */);

@@ -244,6 +244,7 @@ OPT_BOOL(opt_no_fused_lsqr_observer, cfg.no_fused_lsqr_observer)
 OPT_BOOL(opt_no_update_pair, cfg.no_update_pair)
 OPT_BOOL(opt_two_kernel_step, cfg.two_kernel_step)
 OPT_BOOL(opt_warn_generic, warn_generic)
+OPT_BOOL(opt_tall_prologue, cfg.tall_prologue)
 #undef OPT_BOOL
 int opt_max_grid(mi_ctx *c, long v) {
   c->max_grid = (int)std::min<long>(kMaxGrid, std::max<long>(1, v));
@@ -283,7 +284,7 @@ const OptionDesc kOptions[] = {
     {"NO_SPMM_SWEEP", opt_no_spmm_sweep}, {"SWEEP_ZSEGS", opt_sweep_zsegs, true},
     {"NO_ZERO_COPY", opt_no_zero_copy}, {"NO_POLLED_SYNC", opt_no_polled_sync}, {"WIDE_QUAD", opt_wide_quad, true}, {"WIDE_WINDOW", opt_wide_window, true},
     {"NO_UPDATE_MFMA", opt_no_update_mfma}, {"HALO_RPRIME", opt_halo_rprime}, {"NO_GRAM_HALF", opt_no_gram_half}, {"SO3_NO_QUAT", opt_so3_no_quat}, {"SO3_NO_RQUAT", opt_so3_no_rquat}, {"EARLY_S", opt_early_s}, {"DEFER_S", opt_defer_s}, {"NO_FUSED_OBSERVER", opt_no_fused_observer}, {"NO_FUSED_LSQR_OBSERVER", opt_no_fused_lsqr_observer}, {"NO_UPDATE_PAIR", opt_no_update_pair}, {"TWO_KERNEL_STEP", opt_two_kernel_step}, {"SO3_SORT_NBR", opt_so3_sort_nbr, true},
-    {"WARN_GENERIC", opt_warn_generic}, {"REANCHOR", opt_reanchor, true},
+    {"WARN_GENERIC", opt_warn_generic}, {"TALL_PROLOGUE", opt_tall_prologue}, {"REANCHOR", opt_reanchor, true},
 };
 // value of a BOOLEAN switch: an integer; anything else ("yes", "true", "on" -- and the presence-only `MI355OPT_X=` of
 // the r01-r03 scripts) means 1, so that no spelling that used to switch something on is silently off.  An INTEGER-valued

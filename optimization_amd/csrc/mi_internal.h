@@ -27,6 +27,7 @@ constexpr int kWave = 64;
 constexpr int kBlock = 1024;
 constexpr int kWaves = kBlock / kWave;  // 16
 constexpr int kMaxP = 8;                // widest Stiefel / tall-skinny field the templated kernels are instantiated for
+                                        // (rows of 9 ... kMaxPTall = 16 doubles: the tall-row family, stiefel_tall.h)
 constexpr int kMaxGrid = 512;
 constexpr int kMaxRows = 1024;          // partial rows per component (the streaming kernels leave <= kMaxGrid; the
                                         // window kernels, with their smaller workgroups, up to kMaxRows)
@@ -184,6 +185,8 @@ struct Config {
                                     // (r05 form) instead of 32-byte quaternions written by the retraction (r06; creation-time)
   bool so3_no_quat = false;         // SO3_NO_QUAT: the measurements of mi_so3n stay 3 x 3 matrices (r04 form; creation-time)
   int so3_sort_nbr = 0;             // SO3_SORT_NBR: mi_so3n_create orders a node's incidences by neighbour (experiment)
+  bool tall_prologue = false;       // TALL_PROLOGUE: the consumers of the tall-row family (p = 9 ... 16, stiefel_tall.hip) re-reduce the
+                                    // Gram rows in their prologue instead of reading the row of the one-workgroup reduce kernel (A/B)
 };
 
 struct KTimer {

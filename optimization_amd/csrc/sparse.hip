@@ -4,6 +4,7 @@
 //
 // Algorithmic bytes: 12*nnz + 4*(n+1) + 16*n*p.
 #include "spmm_core.h"
+#include "stiefel_tall.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -676,11 +677,15 @@ int mi_csr_destroy(mi_csr *A) {
 
 int mi_csr_spmm(const mi_csr *A, int p, const mi_vec *V, mi_vec *W) {
   MI_REQUIRE(A && V && W, "null argument");
-  MI_REQUIRE(p >= 1 && p <= kMaxP, "p must be in [1,%d], got %d", kMaxP, p);
+  MI_REQUIRE(p >= 1 && p <= kMaxPTall, "p must be in [1,%d], got %d", kMaxPTall, p);
   MI_REQUIRE(V->n == A->n * (size_t)p && W->n == A->n * (size_t)p,
              "SpMM dimension mismatch: A has %zu rows, p=%d, V %zu, W %zu", A->n, p, V->n, W->n);
   MI_REQUIRE(V->d != W->d, "SpMM input and output must not alias");
   touch(W);
+  if (tall_p(p)) {  // rows of 9 ... 16 doubles: the tall-row family (one context)
+    MI_TRY(tall_check(A->ctx, A, A->n, p));
+    return tall_spmm(A->ctx, A, p, V->d, W->d);
+  }
   MI_TRY(comm_halo_exchange(A->ctx, A, p, V->d));
   return csr_spmm_launch(A, p, V->d, W->d);
 }

@@ -1,4 +1,5 @@
-// stiefel.hip -- Stiefel manifold St(n,p) (p <= 8, embedded metric) kernels and the Rayleigh-quotient
+// stiefel.hip -- Stiefel manifold St(n,p) (embedded metric) kernels for p <= 8 -- rows of 9 ... 16 doubles are routed to
+// the tall-row family of stiefel_tall.hip by the entry points below -- and the Rayleigh-quotient
 // problem  f(X) = .5 tr(X' A X):  the Objective / QuadraticModel / RiemannianMetric / Retraction
 // callables a TNT client supplies (Riemannian/Concepts.h:44-112).  The reference ships only the
 // S^2 = St(3,1) lambdas of tests/TNT_unit_test.cpp:73-117; these are their n x p generalisation:
@@ -17,6 +18,7 @@
 #include "comm_ipc.h"
 #include "spmm_core.h"
 #include "stiefel_core.h"
+#include "stiefel_tall.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1188,6 +1190,7 @@ int sharded_reduce(mi_ctx *ctx, int count, int k, double *slots) {
 
 int launch_spmm_gram(mi_ctx *ctx, const mi_csr *A, int p, const CgState *st, const double *V,
                      const double *X, const double *S, double *Z, int *count) {
+  if (tall_p(p)) return tall_spmm_gram(ctx, A, p, st, V, X, S, Z, count);  // rows of 9 ... 16 doubles
   const size_t ngroups = sell_groups(A);
   int grid = uniform_grid(ctx, ngroups);
   MI_TRY(comm_halo_exchange(ctx, A, p, V));
@@ -1214,6 +1217,8 @@ int launch_spmm_gram(mi_ctx *ctx, const mi_csr *A, int p, const CgState *st, con
 // out = Z - X sym(Gram) where the symmetrised Gram partial rows are in ctx->partials2
 int launch_finish(mi_ctx *ctx, size_t n, int p, const CgState *st, const double *X, const double *Z,
                   const double *Vin, int count, double *M_out, double *out, bool dots, int *nparts) {
+  // rows of 9 ... 16 doubles (count = 0: the Gram rows are reduced already, tall_reduce)
+  if (tall_p(p)) return tall_finish(ctx, n, p, st, X, Z, Vin, count, M_out, out, dots, nparts);
   const int grid = row_grid(ctx, n, p);
   double *slots = ctx->scalars + SLOT_GRAM;
   // several ranks: all-reduce the Gram partial rows themselves and keep the prologue re-reduction
@@ -1232,7 +1237,8 @@ int launch_finish(mi_ctx *ctx, size_t n, int p, const CgState *st, const double 
 
 int check_np(mi_ctx *ctx, size_t n, int p, const mi_vec *a, const mi_vec *b, const mi_vec *c) {
   MI_REQUIRE(ctx, "ctx is null");
-  MI_REQUIRE(p >= 1 && p <= kMaxP, "p must be in [1,%d], got %d", kMaxP, p);
+  MI_REQUIRE(p >= 1 && p <= kMaxPTall, "p must be in [1,%d], got %d", kMaxPTall, p);
+  if (tall_p(p)) MI_TRY(tall_check(ctx, nullptr, n, p));  // (one context, fields below 4 GiB)
   const mi_vec *vs[3] = {a, b, c};
   for (const mi_vec *v : vs) {
     if (!v) continue;
@@ -1542,6 +1548,13 @@ int rq_apply_dir(mi_op *self, const mi_vec *in, mi_vec *out, int gram_count, int
   return MI_OK;
 }
 
+// rows of 9 ... 16 doubles: the objective .5 tr(sym(X'AX)) from the reduced 16 x 16 Gram row (tall_reduce) as read back
+double tall_half_trace(const double *G, int p) {
+  double tr = 0;
+  for (int a = 0; a < p; ++a) tr += G[a * 16 + a];
+  return .5 * tr;
+}
+
 struct RqPreconImpl {
   mi_stiefel_rq *q;
   const mi_vec *X;
@@ -1552,6 +1565,11 @@ int rq_precon_apply(mi_precon *self, const mi_vec *r, mi_vec *v) {
   mi_stiefel_rq *q = im->q;
   mi_ctx *ctx = q->ctx;
   const int p = q->p;
+  if (tall_p(p)) {
+    int count = 0;
+    MI_TRY(tall_gram(ctx, q->n, p, 2, true, im->X->d, r->d, im->dinv->d, q->Z->d, &count));
+    return launch_finish(ctx, q->n, p, nullptr, im->X->d, q->Z->d, nullptr, count, nullptr, v->d, false, nullptr);
+  }
   const int grid = row_grid(q->ctx, q->n, p);
   DISPATCH_P(p, hipLaunchKernelGGL((k_st_gram<P, 2, true>), dim3(grid), dim3(StBlk<P>::threads), 0, ctx->stream, q->n,
                                    (const double *)im->X->d, (const double *)r->d,
@@ -1590,6 +1608,19 @@ int mi_debug_stiefel_hess_form(int p, int gram_count, const size_t m[9], const i
 int mi_stiefel_gram(mi_ctx *ctx, size_t n, int p, const mi_vec *X, const mi_vec *Z, double *G_host) {
   MI_TRY(check_np(ctx, n, p, X, Z, nullptr));
   MI_REQUIRE(X && Z && G_host, "null argument");
+  if (tall_p(p)) {  // raw 16 x 16 rows -> the reduced row -> host
+    int count = 0;
+    MI_TRY(tall_gram(ctx, n, p, 0, false, X->d, Z->d, nullptr, nullptr, &count));
+    MI_TRY(tall_reduce(ctx, count));
+    double G[kTallTile];
+    const void *dev[1] = {tall_reduced_row(ctx)};
+    const size_t bytes[1] = {sizeof(G)};
+    void *host[1] = {G};
+    MI_TRY(readback_sync(ctx, 1, dev, bytes, host));
+    for (int a = 0; a < p; ++a)
+      for (int b = 0; b < p; ++b) G_host[a * p + b] = G[a * 16 + b];
+    return MI_OK;
+  }
   const int grid = row_grid(ctx, n, p);
   DISPATCH_P(p, hipLaunchKernelGGL((k_st_gram<P, 0, false>), dim3(grid), dim3(StBlk<P>::threads), 0, ctx->stream, n,
                                    (const double *)X->d, (const double *)Z->d, (const double *)nullptr,
@@ -1603,6 +1634,11 @@ int mi_stiefel_project(mi_ctx *ctx, size_t n, int p, const mi_vec *X, const mi_v
   MI_TRY(check_np(ctx, n, p, X, Z, out));
   MI_REQUIRE(X && Z && out, "null argument");
   touch(out);
+  if (tall_p(p)) {
+    int count = 0;
+    MI_TRY(tall_gram(ctx, n, p, 0, true, X->d, Z->d, nullptr, nullptr, &count));
+    return launch_finish(ctx, n, p, nullptr, X->d, Z->d, nullptr, count, nullptr, out->d, false, nullptr);
+  }
   const int grid = row_grid(ctx, n, p);
   DISPATCH_P(p, hipLaunchKernelGGL((k_st_gram<P, 0, true>), dim3(grid), dim3(StBlk<P>::threads), 0, ctx->stream, n,
                                    (const double *)X->d, (const double *)Z->d, (const double *)nullptr,
@@ -1616,6 +1652,11 @@ int mi_stiefel_retract(mi_ctx *ctx, size_t n, int p, const mi_vec *X, const mi_v
   touch(Y);
   const int grid = row_grid(ctx, n, p);
   KScope ks(ctx, MI_K_STIEFEL_RETRACT);
+  if (tall_p(p)) {  // Y = X + V with the rows of Y'Y, then the polar factor
+    int count = 0;
+    MI_TRY(tall_gram(ctx, n, p, 1, true, X->d, V->d, nullptr, Y->d, &count));
+    return tall_polar(ctx, n, p, Y->d, count);
+  }
   DISPATCH_P(p, hipLaunchKernelGGL((k_st_gram<P, 1, true>), dim3(grid), dim3(StBlk<P>::threads), 0, ctx->stream, n,
                                    (const double *)X->d, (const double *)V->d, (const double *)nullptr,
                                    Y->d, ctx->partials2));
@@ -1634,16 +1675,17 @@ int mi_stiefel_retract(mi_ctx *ctx, size_t n, int p, const mi_vec *X, const mi_v
 
 int mi_stiefel_rq_create(mi_ctx *ctx, const mi_csr *A, size_t n, int p, mi_stiefel_rq **out) {
   MI_REQUIRE(ctx && A && out, "null argument");
-  MI_REQUIRE(p >= 1 && p <= kMaxP, "p must be in [1,%d], got %d", kMaxP, p);
+  MI_REQUIRE(p >= 1 && p <= kMaxPTall, "p must be in [1,%d], got %d", kMaxPTall, p);
   MI_REQUIRE(A->n == n && A->ctx == ctx, "matrix has %zu rows, expected %zu", A->n, n);
+  if (tall_p(p)) MI_TRY(tall_check(ctx, A, n, p));
   mi_stiefel_rq *q = new mi_stiefel_rq();
   q->ctx = ctx;
   q->A = A;
   q->n = n;
   q->p = p;
   q->X = nullptr;
-  MI_HIP(hipMalloc((void **)&q->S_dev, kMaxP * kMaxP * sizeof(double)));
-  MI_HIP(hipMemsetAsync(q->S_dev, 0, kMaxP * kMaxP * sizeof(double), ctx->stream));
+  MI_HIP(hipMalloc((void **)&q->S_dev, kMaxPTall * kMaxPTall * sizeof(double)));
+  MI_HIP(hipMemsetAsync(q->S_dev, 0, kMaxPTall * kMaxPTall * sizeof(double), ctx->stream));
   MI_TRY(mi_vec_create(ctx, n * (size_t)p, &q->Z));
   MI_TRY(mi_vec_create(ctx, n * (size_t)p, &q->Y));
   q->hess.ctx = ctx;
@@ -1678,6 +1720,16 @@ int mi_stiefel_rq_objective(mi_stiefel_rq *q, const mi_vec *X, double *f) {
   q->trial_X = nullptr;  // (Z is scratch of both)
   int count = 0;
   MI_TRY(launch_spmm_gram(ctx, q->A, q->p, nullptr, X->d, X->d, nullptr, q->Z->d, &count));
+  if (tall_p(q->p)) {  // 136 packed entries do not fit the slots of SLOT_GRAM: the reduced row is read back itself
+    MI_TRY(tall_reduce(ctx, count));
+    double Gt[kTallTile];
+    const void *dev[1] = {tall_reduced_row(ctx)};
+    const size_t bytes[1] = {sizeof(Gt)};
+    void *host[1] = {Gt};
+    MI_TRY(readback_sync(ctx, 1, dev, bytes, host));
+    *f = tall_half_trace(Gt, q->p);
+    return MI_OK;
+  }
   double *slots = ctx->scalars + SLOT_GRAM;
   const int ns = nsym(q->p);
   MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, ns, slots));
@@ -1722,7 +1774,9 @@ int mi_stiefel_rq_model(mi_stiefel_rq *q, const mi_vec *X, mi_vec *grad, mi_op *
   q->dg.twok = st_hess_twok_exists(q->p, st_hess_traits(q->ctx, q->A));
   // the one-pass kernel uses 32-bit byte offsets: fields of 4 GiB or more keep the two-pass operator -- and so does
   // a matrix that is not symmetric (checked at creation): the one-pass form replaces X'(A p) by (A X)'p
-  q->hess.dirgram = (sell_stream_ok(q->A, q->p) && q->A->symmetric) ? &q->dg : nullptr;
+  // rows of 9 ... 16 doubles have no one-pass form (st_hess_plan): STPCG drives the two-pass operator through
+  // apply_dots, the three curvature dots fused into its last pass
+  q->hess.dirgram = (sell_stream_ok(q->A, q->p) && q->A->symmetric && !tall_p(q->p)) ? &q->dg : nullptr;
   if (!q->A->symmetric && !q->warned_unsymmetric) {
     q->warned_unsymmetric = true;
     fprintf(stderr, "mi355opt: the matrix of this Stiefel Rayleigh-quotient problem is not symmetric: the Hessian "
@@ -1752,7 +1806,7 @@ int mi_stiefel_rq_trial(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *h, cons
     MI_TRY(mi_vec_create(ctx, N, &q->Y_next));
     MI_TRY(mi_vec_create(ctx, N, &q->grad_next));
     MI_TRY(mi_vec_create(ctx, N, &q->Hh));
-    MI_HIP(hipMalloc((void **)&q->S_next, kMaxP * kMaxP * sizeof(double)));
+    MI_HIP(hipMalloc((void **)&q->S_next, kMaxPTall * kMaxPTall * sizeof(double)));
   }
   q->trial_X = nullptr;
   // (a) Hess h, then |h|^2, <g,h>, <h, Hess h> in one pass (as MI355::dot_batch does)
@@ -1768,12 +1822,26 @@ int mi_stiefel_rq_trial(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *h, cons
   int count = 0;
   MI_TRY(launch_spmm_gram(ctx, q->A, q->p, nullptr, X_trial->d, X_trial->d, nullptr, q->Y_next->d, &count));
   const int ns = nsym(q->p);
-  MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, ns, ctx->scalars + SLOT_GRAM));
-  MI_TRY(launch_finish(ctx, q->n, q->p, nullptr, X_trial->d, q->Y_next->d, nullptr, count, q->S_next,
+  const bool tall = tall_p(q->p);
+  // (rows of 9 ... 16 doubles: the Gram rows are reduced once, into the row the finish pass and the read-back share)
+  if (tall) MI_TRY(tall_reduce(ctx, count));
+  else MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, ns, ctx->scalars + SLOT_GRAM));
+  MI_TRY(launch_finish(ctx, q->n, q->p, nullptr, X_trial->d, q->Y_next->d, nullptr, tall ? 0 : count, q->S_next,
                        q->grad_next->d, false, nullptr));
   {
     const double *xs[1] = {q->grad_next->d}, *ys[1] = {q->grad_next->d};
     MI_TRY(dot_batch_to_slots(ctx, 1, xs, ys, N, SLOT_MISC + 3));
+  }
+  if (tall) {  // (d) one read-back: the reduced Gram row and slots [SLOT_MISC, SLOT_MISC + 4)
+    double Gt[kTallTile], misc[4];
+    const void *dev[2] = {tall_reduced_row(ctx), ctx->scalars + SLOT_MISC};
+    const size_t bytes[2] = {sizeof(Gt), sizeof(misc)};
+    void *host[2] = {Gt, misc};
+    MI_TRY(readback_sync(ctx, 2, dev, bytes, host));
+    out[0] = tall_half_trace(Gt, q->p);
+    for (int i = 0; i < 4; ++i) out[1 + i] = misc[i];
+    q->remember_trial(X_trial);
+    return MI_OK;
   }
   // (d) one read-back: slots [SLOT_GRAM, SLOT_MISC + 4)
   static_assert(SLOT_GRAM < SLOT_MISC && SLOT_MISC + 4 <= kScalarSlots, "slot map");
@@ -1811,7 +1879,7 @@ int mi_stiefel_rq_armijo_trial(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *
     MI_TRY(mi_vec_create(ctx, N, &q->Y_next));
     MI_TRY(mi_vec_create(ctx, N, &q->grad_next));
     MI_TRY(mi_vec_create(ctx, N, &q->Hh));
-    MI_HIP(hipMalloc((void **)&q->S_next, kMaxP * kMaxP * sizeof(double)));
+    MI_HIP(hipMalloc((void **)&q->S_next, kMaxPTall * kMaxPTall * sizeof(double)));
   }
   q->trial_X = nullptr;
   touch(X_trial);
@@ -1820,12 +1888,25 @@ int mi_stiefel_rq_armijo_trial(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *
   int count = 0;
   MI_TRY(launch_spmm_gram(ctx, q->A, q->p, nullptr, X_trial->d, X_trial->d, nullptr, q->Y_next->d, &count));
   const int ns = nsym(q->p);
-  MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, ns, ctx->scalars + SLOT_GRAM));
-  MI_TRY(launch_finish(ctx, q->n, q->p, nullptr, X_trial->d, q->Y_next->d, nullptr, count, q->S_next,
+  const bool tall = tall_p(q->p);
+  if (tall) MI_TRY(tall_reduce(ctx, count));
+  else MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, ns, ctx->scalars + SLOT_GRAM));
+  MI_TRY(launch_finish(ctx, q->n, q->p, nullptr, X_trial->d, q->Y_next->d, nullptr, tall ? 0 : count, q->S_next,
                        q->grad_next->d, false, nullptr));
   {
     const double *xs[1] = {q->grad_next->d}, *ys[1] = {q->grad_next->d};
     MI_TRY(dot_batch_to_slots(ctx, 1, xs, ys, N, SLOT_MISC));
+  }
+  if (tall) {  // one read-back: the reduced Gram row and slot SLOT_MISC
+    double Gt[kTallTile], misc[1];
+    const void *dev[2] = {tall_reduced_row(ctx), ctx->scalars + SLOT_MISC};
+    const size_t bytes[2] = {sizeof(Gt), sizeof(misc)};
+    void *host[2] = {Gt, misc};
+    MI_TRY(readback_sync(ctx, 2, dev, bytes, host));
+    out[0] = tall_half_trace(Gt, q->p);
+    out[1] = misc[0];
+    q->remember_trial(X_trial);
+    return MI_OK;
   }
   double buf[SLOT_MISC + 1 - SLOT_GRAM];
   MI_TRY(read_slots_sync(ctx, SLOT_GRAM, SLOT_MISC + 1 - SLOT_GRAM, buf));
