@@ -107,6 +107,7 @@ enum {
   MI_K_COMM_ALLREDUCE, /* a scalar exchange across ranks that is a launch of its own: one RCCL all-reduce (group) or
                           one exchange kernel of the peer-memory layer; folded exchanges have none */
   MI_K_COMM_HALO,      /* a halo exchange that is a launch of its own: ncclSend/ncclRecv group or push kernel */
+  MI_K_SO3_GRAD,        /* the gradient-only assembly pass of mi_so3n_gradient / mi_so3n_armijo_trial */
   MI_K_COUNT
 };
 /* The library's switches (A/B forms of its kernels, verification hooks of the multi-rank path) are read from the
@@ -488,6 +489,21 @@ MI_API int mi_so3n_retract(mi_so3n *prob, const mi_vec *R, const mi_vec *xi, mi_
  * has the bits the separate calls would produce. */
 MI_API int mi_so3n_trial(mi_so3n *prob, const mi_vec *R, const mi_vec *h, const mi_vec *g, int with_precon,
                          mi_vec *R_trial, double out[6]);
+/* VectorField (Riemannian/GradientDescent.h:216,325): grad f(R) in so(3)^N coordinates through the gradient-only form
+ * of the assembly pass -- no Hessian blocks, no diagonal blocks, no model bound; no sync.  The bits of the gradient
+ * mi_so3n_model writes.  If R is the point the last mi_so3n_armijo_trial evaluated the gradient found there is copied
+ * and nothing is assembled; likewise for the point of the last mi_so3n_trial, whose speculative model stays in place
+ * for a following mi_so3n_model(prob, R, ...). */
+MI_API int mi_so3n_gradient(mi_so3n *prob, const mi_vec *R, mi_vec *grad);
+/* One Armijo trial of a backtracking line search along -g (Riemannian/GradientDescent.h:266-286: h = -t g, R_trial =
+ * retract(R, h), f(R_trial)) plus, speculatively, the gradient at the trial point and its squared norm (:323-327): one
+ * launch chain, ONE read-back (sync).  out[2] = {f(R+), |grad f(R+)|^2}; h_out receives -t g.  Needs no bound model.
+ * A following mi_so3n_gradient(prob, R_trial, ...) copies the gradient; a following mi_so3n_model(prob, R_trial, ...)
+ * assembles the full model (only the gradient exists).  R_trial must not alias R, h_out must not alias g.  Every number
+ * has the bits the separate calls (mi_vec_scale_to, mi_so3n_retract, mi_so3n_objective, mi_so3n_gradient, mi_vec_dot)
+ * would produce. */
+MI_API int mi_so3n_armijo_trial(mi_so3n *prob, const mi_vec *R, const mi_vec *g, double t, mi_vec *h_out,
+                                mi_vec *R_trial, double out[2]);
 
 /* ---------------------------------------------------------------------------------------------
  * (8) LOBPCG building blocks (LinearAlgebra/LOBPCG.h:131-337).  Panels are column-major m x k

@@ -18,7 +18,7 @@ STATUS = {0: "MI_OK", 1: "MI_ERR_INVALID_ARGUMENT", 2: "MI_ERR_HIP", 3: "MI_ERR_
 KERNELS = ["none", "cg_init", "cg_dot3", "cg_scalar_a", "cg_update", "cg_scalar_b", "cg_pupdate",
            "csr_spmm", "stiefel_spmm_gram", "stiefel_gram_reduce", "stiefel_finish_dots",
            "stiefel_retract", "bsr3_spmv_dots", "blas1", "lobpcg_gram", "lobpcg_update",
-           "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo"]
+           "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo", "so3_grad"]
 KID = {k: i for i, k in enumerate(KERNELS)}
 STPCG_EXIT = ["RESIDUAL", "MAXIT", "KERNEL", "BOUNDARY", "USER"]
 
@@ -199,6 +199,8 @@ def load():
         "mi_so3n_model": [vp, vp, vp, C.POINTER(vp), C.POINTER(vp)],
         "mi_so3n_retract": [vp, vp, vp, vp],
         "mi_so3n_trial": [vp, vp, vp, vp, C.c_int, vp, c_double_p],
+        "mi_so3n_gradient": [vp, vp, vp],
+        "mi_so3n_armijo_trial": [vp, vp, vp, C.c_double, vp, vp, c_double_p],
         "mi_stpcg_collect": [vp, C.POINTER(StpcgResult)],
         "mi_lobpcg_gram": [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, c_double_p],
         "mi_lobpcg_update": [vp, C.c_size_t, C.c_int, C.c_int, vp, c_double_p, C.c_int, vp],
@@ -1121,6 +1123,20 @@ class So3N:
         out = np.zeros(6)
         check(self.L.mi_so3n_trial(self.h, R.h, h.h, g.h, int(with_precon), Rt.h, _dp(out)))
         return Rt, dict(f=out[0], hh=out[1], gh=out[2], hHh=out[3], grad_sqnorm=out[4], precon_grad_sqnorm=out[5])
+
+    def gradient(self, R, out=None):
+        """mi_so3n_gradient: grad f(R) (3N) through the gradient-only pass, or the copy of a trial's"""
+        g = out if out is not None else Vec(self.ctx, 3 * self.N)
+        check(self.L.mi_so3n_gradient(self.h, R.h, g.h))
+        return g
+
+    def armijo_trial(self, R, g, t, h=None, R_trial=None):
+        """mi_so3n_armijo_trial: (h = -t g Vec, R_trial Vec, dict(f, grad_sqnorm))"""
+        h = h if h is not None else Vec(self.ctx, 3 * self.N)
+        Rt = R_trial if R_trial is not None else Vec(self.ctx, 9 * self.N)
+        out = np.zeros(2)
+        check(self.L.mi_so3n_armijo_trial(self.h, R.h, g.h, float(t), h.h, Rt.h, _dp(out)))
+        return h, Rt, dict(f=out[0], grad_sqnorm=out[1])
 
     def __del__(self):
         try:

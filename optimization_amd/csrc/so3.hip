@@ -125,7 +125,12 @@ __global__ __launch_bounds__(256) void k_so3_quat(size_t N, const double *__rest
 // across a 128-byte line; two 16-byte loads) and expanded, instead of as nine doubles at a 72-byte stride (1.56 lines on
 // average).  Rq is written by the retraction of the trial step (k_so3_retract<true>) or, for a point the library did not
 // produce, by k_so3_quat right before the assembly.  The own rotation R_i is read from R itself.
-template <bool MODEL, bool SQ, bool GQ>
+// FORM: what the incidence loop leaves behind.  SO3_OBJECTIVE: the objective partial only; SO3_MODEL: gradient, Hessian
+// blocks, diagonal blocks and their inverses; SO3_GRAD: the gradient only (GradientDescent: mi_so3n_gradient,
+// mi_so3n_armijo_trial) -- the same EG / facc / degw accumulation in the same order, without Q = R_i' R_j, the three
+// q_hat_basis columns, Bblk, Dsl and Dinv (72 bytes per incidence slot and 144 + 72 bytes per node that nobody reads).
+enum { SO3_OBJECTIVE = 0, SO3_MODEL = 1, SO3_GRAD = 2 };
+template <int FORM, bool SQ, bool GQ>
 __device__ __forceinline__ void so3_model_slice(const IncView &inc, const double *__restrict__ R,
                                                 const double *__restrict__ Rq,
                                                 const double *__restrict__ Sinc, const double *__restrict__ winc,
@@ -187,7 +192,7 @@ __device__ __forceinline__ void so3_model_slice(const IncView &inc, const double
       }
       facc += we * q;
       degw += we;
-      if (!MODEL) continue;
+      if (FORM != SO3_MODEL) continue;
       double Q[9];
       mat3_mul_at(Ri, Rj, Q);  // R_i' R_j
 #pragma unroll
@@ -201,20 +206,23 @@ __device__ __forceinline__ void so3_model_slice(const IncView &inc, const double
         Bk[2 * 3 + m] = we * col[2];
       }
     }
-    if (MODEL) {
+    if (FORM == SO3_MODEL) {
 #pragma unroll
       for (int c = 0; c < 9; ++c) Bblk[((size_t)k * 9 + c) * 64 + lane] = Bk[c];
     }
   }
-  if (!MODEL) return;
+  if (FORM == SO3_OBJECTIVE) return;
   if (!live) {
+    if (FORM == SO3_MODEL) {
 #pragma unroll
-    for (int c = 0; c < 9; ++c) Dsl[(slice * 9 + c) * 64 + lane] = 0.0;
+      for (int c = 0; c < 9; ++c) Dsl[(slice * 9 + c) * 64 + lane] = 0.0;
+    }
     return;
   }
   double Q[9], C[9];
   mat3_mul_at(Ri, EG, Q);
   vee_skew2(Q, grad + 3 * i);
+  if (FORM == SO3_GRAD) return;
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -248,7 +256,7 @@ __global__ __launch_bounds__(256) void k_so3_model(IncView inc, const double *__
   double facc = 0;
   const size_t ngroups = (inc.nslices + 3) / 4;
   for (size_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x)
-    so3_model_slice<MODEL, SQ, GQ>(inc, R, Rq, Sinc, winc, grad, Dinv, Bblk, Dsl, grp * 4 + w, lane, facc);
+    so3_model_slice<MODEL ? SO3_MODEL : SO3_OBJECTIVE, SQ, GQ>(inc, R, Rq, Sinc, winc, grad, Dinv, Bblk, Dsl, grp * 4 + w, lane, facc);
   // the workgroup's partial of the objective: workgroup b -> row b % kMaxRows of component b / kMaxRows (one workgroup
   // per group of slices keeps the dynamic balance of ~2000 short workgroups: a grid capped at kMaxRows rows cost the
   // assembly 30 us at N = 5e5); the components are added in fixed order by k_sum_slots
@@ -258,6 +266,29 @@ __global__ __launch_bounds__(256) void k_so3_model(IncView inc, const double *__
   if (threadIdx.x == 0) {
     fpartials[(size_t)(blockIdx.x / kMaxRows) * kMaxRows + blockIdx.x % kMaxRows] = (flds[0] + flds[1]) + (flds[2] + flds[3]);
     // the rows of the last component past the last workgroup read as zero (the buffer is shared with other reductions)
+    const size_t total = (size_t)((gridDim.x + kMaxRows - 1) / kMaxRows) * kMaxRows, z = (size_t)gridDim.x + blockIdx.x;
+    if (z < total) fpartials[z] = 0.0;
+  }
+}
+// The gradient-only form: grid, workgroup shape and objective partial rows of k_so3_model (see there), so that
+// model_objective_to_slot reduces f exactly as mi_so3n_objective does; the gradient bit for bit the one
+// k_so3_model<true> writes.  (A kernel of its own, not a third value of MODEL: the existing instantiations keep their
+// names and their code.)
+template <bool SQ, bool GQ>
+__global__ __launch_bounds__(256) void k_so3_grad(IncView inc, const double *__restrict__ R, const double *__restrict__ Rq,
+                                                  const double *__restrict__ Sinc, const double *__restrict__ winc,
+                                                  double *__restrict__ grad, double *__restrict__ fpartials) {
+  __shared__ double flds[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double facc = 0;
+  const size_t ngroups = (inc.nslices + 3) / 4;
+  for (size_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x)
+    so3_model_slice<SO3_GRAD, SQ, GQ>(inc, R, Rq, Sinc, winc, grad, nullptr, nullptr, nullptr, grp * 4 + w, lane, facc);
+  facc = wave_reduce_sum(facc);
+  if (lane == 0) flds[w] = facc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    fpartials[(size_t)(blockIdx.x / kMaxRows) * kMaxRows + blockIdx.x % kMaxRows] = (flds[0] + flds[1]) + (flds[2] + flds[3]);
     const size_t total = (size_t)((gridDim.x + kMaxRows - 1) / kMaxRows) * kMaxRows, z = (size_t)gridDim.x + blockIdx.x;
     if (z < total) fpartials[z] = 0.0;
   }
@@ -399,6 +430,15 @@ struct mi_so3n {
   bool is_trial(const mi_vec *X) const {
     return trial_R == X && trial_d == X->d && trial_serial == X->serial && trial_gen == gen_of(X);
   }
+  // mi_so3n_armijo_trial: the point whose GRADIENT ONLY sits in grad_next (the Hessian-sized _next arrays hold nothing,
+  // or the model of an older trial point: mi_so3n_model must not swap them in) -- a key of its own, same contents
+  // identity.  At most one of the two keys is live: whoever fills grad_next drops the other kind's.
+  const mi_vec *armijo_R = nullptr;
+  const double *armijo_d = nullptr;
+  uint64_t armijo_serial = 0, armijo_gen = 0;
+  bool is_armijo(const mi_vec *X) const {
+    return armijo_R == X && armijo_d == X->d && armijo_serial == X->serial && armijo_gen == gen_of(X);
+  }
 };
 
 namespace {
@@ -428,6 +468,20 @@ void launch_model(mi_so3n *q, bool model, int grid, const double *R, double *gra
   else { if (q->sinc_quat) { SO3M_G(false, true); } else { SO3M_G(false, false); } }
 #undef SO3M_G
 #undef SO3M
+}
+// the gradient-only form of the assembly (k_so3_grad) on launch_model's grid, objective partials into ctx->partials2
+void launch_grad(mi_so3n *q, int grid, const double *R, double *grad, bool have_quat) {
+  mi_ctx *ctx = q->ctx;
+  const bool gq = q->Rq != nullptr;
+  if (gq && !have_quat)
+    hipLaunchKernelGGL(k_so3_quat, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, R, q->Rq);
+  KScope ks(ctx, MI_K_SO3_GRAD);
+#define SO3G(SQV, GQV)                                                                                              \
+  hipLaunchKernelGGL((k_so3_grad<SQV, GQV>), dim3(grid), dim3(256), 0, ctx->stream, view(q), R, (const double *)q->Rq, \
+                     (const double *)q->Sinc, (const double *)q->winc, grad, ctx->partials2)
+  if (q->sinc_quat) { if (gq) SO3G(true, true); else SO3G(true, false); }
+  else { if (gq) SO3G(false, true); else SO3G(false, false); }
+#undef SO3G
 }
 // the objective partials the assembly left in ctx->partials2 -> one (all-reduced) sum in slots[0]
 int model_objective_to_slot(mi_so3n *q, int grid, double *slot) {
@@ -685,6 +739,7 @@ int mi_so3n_model(mi_so3n *q, const mi_vec *R, mi_vec *grad, mi_op **hess, mi_pr
   mi_ctx *ctx = q->ctx;
   if (q->is_trial(R)) {
     // R is the point mi_so3n_trial just evaluated: its model exists already
+    // (the point of an Armijo trial is NOT one: only its gradient exists -- the full assembly below)
     std::swap(q->Dinv, q->Dinv_next);
     std::swap(q->Bblk, q->Bblk_next);
     std::swap(q->Dsl, q->Dsl_next);
@@ -695,6 +750,7 @@ int mi_so3n_model(mi_so3n *q, const mi_vec *R, mi_vec *grad, mi_op **hess, mi_pr
     MI_HIP(hipGetLastError());
   }
   q->trial_R = nullptr;
+  q->armijo_R = nullptr;
   q->R = R;
   q->R_serial = R->serial;
   if (hess) *hess = &q->hess;
@@ -728,15 +784,16 @@ int mi_so3n_trial(mi_so3n *q, const mi_vec *R, const mi_vec *h, const mi_vec *g,
   mi_ctx *ctx = q->ctx;
   ctx->fusion.fused_trial_steps++;
   const size_t N3 = 3 * q->N;
-  if (!q->grad_next) {
+  if (!q->grad_next) MI_TRY(mi_vec_create(ctx, N3, &q->grad_next));  // (shared with mi_so3n_armijo_trial)
+  if (!q->Dinv_next) {
     MI_TRY(mi_vec_create(ctx, 9 * q->N, &q->Dinv_next));
-    MI_TRY(mi_vec_create(ctx, N3, &q->grad_next));
     MI_TRY(mi_vec_create(ctx, N3, &q->Hh));
     MI_TRY(mi_vec_create(ctx, N3, &q->Pg));
     MI_HIP(hipMalloc((void **)&q->Bblk_next, std::max<size_t>(1, q->padded * 9) * sizeof(double)));
     MI_HIP(hipMalloc((void **)&q->Dsl_next, q->nslices * 9 * 64 * sizeof(double)));
   }
   q->trial_R = nullptr;
+  q->armijo_R = nullptr;  // (grad_next is about to be overwritten)
   // (a) Hess h, then |h|^2, <g,h>, <h, Hess h> in one pass (as MI355::dot_batch does)
   MI_TRY(so3_apply(&q->hess, h, q->Hh));
   {
@@ -787,6 +844,78 @@ int mi_so3n_trial(mi_so3n *q, const mi_vec *R, const mi_vec *h, const mi_vec *g,
   q->trial_d = R_trial->d;
   q->trial_serial = R_trial->serial;
   q->trial_gen = gen_of(R_trial);
+  return MI_OK;
+}
+
+// Without a device the answer is MI_ERR_NO_DEVICE whatever the arguments (no context can exist); with one, a null
+// argument is the usual MI_ERR_INVALID_ARGUMENT.
+#define SO3_REQUIRE_ARGS(COND)                 \
+  do {                                         \
+    if (!(COND)) {                             \
+      MI_TRY(ensure_device());                 \
+      MI_REQUIRE(false, "null argument");      \
+    }                                          \
+  } while (0)
+
+int mi_so3n_gradient(mi_so3n *q, const mi_vec *R, mi_vec *grad) {
+  SO3_REQUIRE_ARGS(q && R && grad);
+  MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
+  MI_REQUIRE(grad->ctx == q->ctx && grad->n == 3 * q->N, "gradient must hold 3N doubles");
+  if (q->is_armijo(R) || q->is_trial(R)) {
+    // the last Armijo trial (or, speculatively, the last trust-region trial) evaluated this very point: its gradient is
+    // there.  Neither key is consumed: a following mi_so3n_model(R) still finds the speculative model of a TNT trial.
+    return mi_vec_copy(grad, q->grad_next);
+  }
+  touch(grad);
+  launch_grad(q, model_grid(q), R->d, grad->d, false);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+int mi_so3n_armijo_trial(mi_so3n *q, const mi_vec *R, const mi_vec *g, double t, mi_vec *h_out, mi_vec *R_trial,
+                         double out[2]) {
+  SO3_REQUIRE_ARGS(q && R && g && h_out && R_trial && out);
+  MI_REQUIRE(R->ctx == q->ctx && g->ctx == q->ctx && h_out->ctx == q->ctx && R_trial->ctx == q->ctx,
+             "vector belongs to another context");
+  MI_REQUIRE(R->n == 9 * q->N && R_trial->n == 9 * q->N && g->n == 3 * q->N && h_out->n == 3 * q->N, "dimension mismatch");
+  MI_REQUIRE(R_trial->d != R->d, "the trial point must not alias the current one");
+  MI_REQUIRE(h_out->d != g->d, "the step must not alias the gradient");
+  mi_ctx *ctx = q->ctx;
+  ctx->fusion.fused_trial_steps++;
+  const size_t N3 = 3 * q->N;
+  if (!q->grad_next) MI_TRY(mi_vec_create(ctx, N3, &q->grad_next));  // (none of the Hessian-sized _next arrays)
+  q->trial_R = nullptr;  // (grad_next is about to be overwritten: the speculative model loses its gradient)
+  q->armijo_R = nullptr;
+  // (a) h = -t g: the kernel of DeviceVector's `-t * g` (mi_vec_scale_to), then R+ = R exp(hat h) with the quaternions
+  // of R+, the gather records of the pass below (k_so3_retract<true>, as in mi_so3n_trial)
+  MI_TRY(mi_vec_scale_to(h_out, -t, g));
+  if (q->Rq) {
+    touch(R_trial);
+    hipLaunchKernelGGL(k_so3_retract<true>, dim3(grid_for(ctx, q->N, 1)), dim3(kBlock), 0, ctx->stream, q->N,
+                       (const double *)R->d, (const double *)h_out->d, R_trial->d, q->Rq);
+    MI_HIP(hipGetLastError());
+  } else {
+    MI_TRY(mi_so3n_retract(q, R, h_out, R_trial));
+  }
+  // (b) grad f(R+) with the partials of f(R+) from the same pass, reduced exactly as mi_so3n_objective does
+  const int grid = model_grid(q);
+  launch_grad(q, grid, R_trial->d, q->grad_next->d, q->Rq != nullptr);
+  MI_HIP(hipGetLastError());
+  MI_TRY(model_objective_to_slot(q, grid, ctx->scalars + SLOT_MISC));
+  // (c) |grad f(R+)|^2 as metric(g, g) forms it (mi_vec_dot)
+  {
+    const double *xs[1] = {q->grad_next->d}, *ys[1] = {q->grad_next->d};
+    MI_TRY(dot_batch_to_slots(ctx, 1, xs, ys, N3, SLOT_MISC + 1));
+  }
+  // (d) one read-back
+  double buf[2];
+  MI_TRY(read_slots_sync(ctx, SLOT_MISC, 2, buf));
+  out[0] = .25 * buf[0];  // (every edge from both ends)
+  out[1] = buf[1];
+  q->armijo_R = R_trial;
+  q->armijo_d = R_trial->d;
+  q->armijo_serial = R_trial->serial;
+  q->armijo_gen = gen_of(R_trial);
   return MI_OK;
 }
 

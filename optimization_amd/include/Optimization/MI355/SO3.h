@@ -58,7 +58,9 @@ class RotationAveraging {
     return FrobeniusMetric{};
   }
   // R_i exp(hat(xi_i)) -- tagged: TNT evaluates a whole trial step (retraction, f at the trial point, the
-  // predicted-decrease terms, the model and both gradient norms at the trial point) through mi_so3n_trial, one read-back
+  // predicted-decrease terms, the model and both gradient norms at the trial point) through mi_so3n_trial, one read-back;
+  // GradientDescent evaluates a whole Armijo trial (h = -t g, retraction, f and the gradient norm at the trial point)
+  // through mi_so3n_armijo_trial, one read-back
   template <typename... Args>
   Riemannian::Retraction<Vector, Vector, Args...> retraction() {
     DeviceTrialRetraction r;
@@ -81,7 +83,27 @@ class RotationAveraging {
       t.precon_grad_trial_sqnorm = out[5];
       return t;
     };
+    r.armijo = [this](const Vector &R, const Vector &g, double t) {
+      DeviceTrialRetraction::ArmijoTrial a;
+      a.h = Vector::like(g);
+      a.x_trial = Vector::like(R);
+      double out[2];
+      check(mi_so3n_armijo_trial(prob_, R.handle(), g.handle(), t, a.h.handle(), a.x_trial.handle(), out));
+      a.f_trial = out[0];
+      a.grad_trial_sqnorm = out[1];
+      return a;
+    };
     return r;
+  }
+  // grad f(R) in so(3)^N coordinates as a VectorField (GradientDescent's interface): the gradient-only assembly pass --
+  // no Hessian blocks, nothing bound; after a fused trial at R it is already there
+  template <typename... Args>
+  Riemannian::VectorField<Vector, Vector, Args...> gradient() {
+    return DeviceGradientField{this, [this](const Vector &R) {
+                                 Vector grad(ctx_, 3 * N_);
+                                 check(mi_so3n_gradient(prob_, R.handle(), grad.handle()));
+                                 return grad;
+                               }};
   }
   // the same without the tag (one call per statement of the reference's loop)
   Riemannian::Retraction<Vector, Vector> plain_retraction() {
