@@ -301,6 +301,25 @@ inline void touch(mi_vec *v) {
   if (v) ++(v->root ? v->root : v)->gen;
 }
 inline uint64_t gen_of(const mi_vec *v) { return (v->root ? v->root : v)->gen; }
+// "This vector with these contents": the key of what a problem object worked out speculatively at a point (the trial
+// points of stiefel.hip and so3.hip).  Handle AND device pointer AND serial AND generation: handles and pooled device
+// pointers are both recycled, and an in-place write must invalidate the speculation too.
+struct VecKey {
+  const mi_vec *v = nullptr;
+  const double *d = nullptr;
+  uint64_t serial = 0, gen = 0;
+  void set(const mi_vec *x) {
+    v = x;
+    d = x->d;
+    serial = x->serial;
+    gen = gen_of(x);
+  }
+  void clear() { v = nullptr; }
+  bool is(const mi_vec *x) const { return v == x && d == x->d && serial == x->serial && gen == gen_of(x); }
+};
+// The weaker "the model is bound to this vector": handle and serial only (handles are recycled) -- the point of a model
+// may be written in place
+inline bool bound_to(const mi_vec *bound, uint64_t serial, const mi_vec *x) { return x && bound == x && serial == x->serial; }
 }  // namespace mi
 
 namespace mi {

@@ -273,7 +273,9 @@ __global__ __launch_bounds__(256) void k_so3_model(IncView inc, const double *__
 // The gradient-only form: grid, workgroup shape and objective partial rows of k_so3_model (see there), so that
 // model_objective_to_slot reduces f exactly as mi_so3n_objective does; the gradient bit for bit the one
 // k_so3_model<true> writes.  (A kernel of its own, not a third value of MODEL: the existing instantiations keep their
-// names and their code.)
+// names and their code.  The lines around the slice walk are repeated here on purpose: as one inlined function shared with
+// k_so3_model they compile to other register counts in the 9-component-measurement forms -- k_so3_model<true, false,
+// false> 166 -> 172 VGPRs, 3 -> 2 waves per SIMD)
 template <bool SQ, bool GQ>
 __global__ __launch_bounds__(256) void k_so3_grad(IncView inc, const double *__restrict__ R, const double *__restrict__ Rq,
                                                   const double *__restrict__ Sinc, const double *__restrict__ winc,
@@ -418,27 +420,17 @@ struct mi_so3n {
   mi_op hess;
   mi_precon bj;
   const mi_vec *R = nullptr;                // the point the model is bound to (mi_so3n_model) ...
-  uint64_t R_serial = 0;                    // ... by handle AND serial (handles are recycled)
+  uint64_t R_serial = 0;                    // ... by handle AND serial (mi::bound_to)
   // mi_so3n_trial: the model assembled speculatively at the trial point (a second set of the arrays above plus the
   // gradient), swapped in by the next mi_so3n_model call if that call is for the same vector -- keyed on the
-  // handle AND the identity of its contents (mi_vec::serial / gen), as in stiefel.hip
+  // handle AND the identity of its contents (mi::VecKey), as in stiefel.hip
   mi_vec *Dinv_next = nullptr, *grad_next = nullptr, *Hh = nullptr, *Pg = nullptr;
   double *Bblk_next = nullptr, *Dsl_next = nullptr;
-  const mi_vec *trial_R = nullptr;
-  const double *trial_d = nullptr;
-  uint64_t trial_serial = 0, trial_gen = 0;
-  bool is_trial(const mi_vec *X) const {
-    return trial_R == X && trial_d == X->d && trial_serial == X->serial && trial_gen == gen_of(X);
-  }
+  VecKey trial;
   // mi_so3n_armijo_trial: the point whose GRADIENT ONLY sits in grad_next (the Hessian-sized _next arrays hold nothing,
   // or the model of an older trial point: mi_so3n_model must not swap them in) -- a key of its own, same contents
   // identity.  At most one of the two keys is live: whoever fills grad_next drops the other kind's.
-  const mi_vec *armijo_R = nullptr;
-  const double *armijo_d = nullptr;
-  uint64_t armijo_serial = 0, armijo_gen = 0;
-  bool is_armijo(const mi_vec *X) const {
-    return armijo_R == X && armijo_d == X->d && armijo_serial == X->serial && armijo_gen == gen_of(X);
-  }
+  VecKey armijo;
 };
 
 namespace {
@@ -450,38 +442,25 @@ int model_grid(const mi_so3n *q) { return (int)std::min<size_t>((q->nslices + 3)
 IncView view(const mi_so3n *q) {
   return IncView{q->N, q->nslices, q->slice_ptr, q->perm, q->nbr};
 }
-// the assembly (model = true) or its objective alone, objective partials into ctx->partials2
+// the assembly in one of its forms (SO3_OBJECTIVE: no outputs; SO3_GRAD: grad only), objective partials into ctx->partials2
 // have_quat: q->Rq already holds the quaternions of R (the trial step's retraction wrote them); otherwise they are formed
 // here first (one pass over R: a point the library did not produce -- the start, or the statement sequence's calls)
-void launch_model(mi_so3n *q, bool model, int grid, const double *R, double *grad, double *Dinv, double *Bblk, double *Dsl,
-                  bool have_quat = false) {
+void launch_assembly(mi_so3n *q, int form, int grid, const double *R, double *grad, double *Dinv, double *Bblk, double *Dsl,
+                     bool have_quat = false) {
   mi_ctx *ctx = q->ctx;
   const bool gq = q->Rq != nullptr;
+  const double *Rq = q->Rq, *Sinc = q->Sinc, *winc = q->winc;
   if (gq && !have_quat)
     hipLaunchKernelGGL(k_so3_quat, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, R, q->Rq);
-#define SO3M(MV, SQV, GQV)                                                                                      \
-  hipLaunchKernelGGL((k_so3_model<MV, SQV, GQV>), dim3(grid), dim3(256), 0, ctx->stream, view(q), R,             \
-                     (const double *)q->Rq, (const double *)q->Sinc, (const double *)q->winc, grad, Dinv, Bblk, Dsl, \
-                     ctx->partials2)
-#define SO3M_G(MV, SQV) if (gq) SO3M(MV, SQV, true); else SO3M(MV, SQV, false)
-  if (model) { if (q->sinc_quat) { SO3M_G(true, true); } else { SO3M_G(true, false); } }
-  else { if (q->sinc_quat) { SO3M_G(false, true); } else { SO3M_G(false, false); } }
-#undef SO3M_G
-#undef SO3M
-}
-// the gradient-only form of the assembly (k_so3_grad) on launch_model's grid, objective partials into ctx->partials2
-void launch_grad(mi_so3n *q, int grid, const double *R, double *grad, bool have_quat) {
-  mi_ctx *ctx = q->ctx;
-  const bool gq = q->Rq != nullptr;
-  if (gq && !have_quat)
-    hipLaunchKernelGGL(k_so3_quat, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, R, q->Rq);
-  KScope ks(ctx, MI_K_SO3_GRAD);
-#define SO3G(SQV, GQV)                                                                                              \
-  hipLaunchKernelGGL((k_so3_grad<SQV, GQV>), dim3(grid), dim3(256), 0, ctx->stream, view(q), R, (const double *)q->Rq, \
-                     (const double *)q->Sinc, (const double *)q->winc, grad, ctx->partials2)
-  if (q->sinc_quat) { if (gq) SO3G(true, true); else SO3G(true, false); }
-  else { if (gq) SO3G(false, true); else SO3G(false, false); }
-#undef SO3G
+  DISPATCH_3(form, FORM, SO3_OBJECTIVE, SO3_MODEL, SO3_GRAD, DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(gq, GQ,
+      if (FORM == SO3_GRAD) {
+        KScope ks(ctx, MI_K_SO3_GRAD);
+        hipLaunchKernelGGL((k_so3_grad<SQ, GQ>), dim3(grid), dim3(256), 0, ctx->stream, view(q), R, Rq, Sinc, winc, grad,
+                           ctx->partials2);
+      } else {
+        hipLaunchKernelGGL((k_so3_model<FORM == SO3_MODEL, SQ, GQ>), dim3(grid), dim3(256), 0, ctx->stream, view(q), R, Rq,
+                           Sinc, winc, grad, Dinv, Bblk, Dsl, ctx->partials2);
+      })));
 }
 // the objective partials the assembly left in ctx->partials2 -> one (all-reduced) sum in slots[0]
 int model_objective_to_slot(mi_so3n *q, int grid, double *slot) {
@@ -495,7 +474,6 @@ int model_objective_to_slot(mi_so3n *q, int grid, double *slot) {
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
-
 
 int so3_apply_common(mi_op *self, const mi_vec *in, mi_vec *out, bool dots, int *nparts) {
   mi_so3n *q = (mi_so3n *)self->impl;
@@ -528,6 +506,31 @@ int so3_bj_apply(mi_precon *self, const mi_vec *r, mi_vec *v) {
   const int s = mi_precon_apply(tmp, r, v);
   mi_precon_destroy(tmp);
   return s;
+}
+
+// Y = R exp(hat xi) as a trial point: a problem that gathers quaternions gets those of Y in q->Rq from the same kernel
+// (the bits k_so3_quat would give), so the assembly at Y needs no conversion pass
+int retract_trial(mi_so3n *q, const mi_vec *R, const mi_vec *xi, mi_vec *Y) {
+  if (!q->Rq) return mi_so3n_retract(q, R, xi, Y);
+  touch(Y);
+  hipLaunchKernelGGL(k_so3_retract<true>, dim3(grid_for(q->ctx, q->N, 1)), dim3(kBlock), 0, q->ctx->stream, q->N,
+                     (const double *)R->d, (const double *)xi->d, Y->d, q->Rq);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+// The tail of both trial steps: the assembly at the trial point retract_trial produced, in the given form, the gradient
+// into grad_next and the other outputs where the caller says; the sum of the objective partials of the same pass,
+// reduced exactly as mi_so3n_objective does, into slot f_slot; |grad f(R+)|^2 as metric(g, g) forms it (mi_vec_dot)
+// into slot g2_slot
+int trial_tail(mi_so3n *q, int form, const mi_vec *R_trial, double *Dinv, double *Bblk, double *Dsl, int f_slot,
+               int g2_slot) {
+  mi_ctx *ctx = q->ctx;
+  const int grid = model_grid(q);
+  launch_assembly(q, form, grid, R_trial->d, q->grad_next->d, Dinv, Bblk, Dsl, q->Rq != nullptr);
+  MI_HIP(hipGetLastError());
+  MI_TRY(model_objective_to_slot(q, grid, ctx->scalars + f_slot));
+  const double *gn[1] = {q->grad_next->d};
+  return dot_batch_to_slots(ctx, 1, gn, gn, 3 * q->N, g2_slot);
 }
 
 }  // namespace
@@ -722,7 +725,7 @@ int mi_so3n_objective(mi_so3n *q, const mi_vec *R, double *f) {
   // the incidence form of the sum (r05): the loop of the model assembly without its outputs -- what mi_so3n_trial gets
   // from the assembly at the trial point itself, bit for bit
   const int grid = model_grid(q);
-  launch_model(q, false, grid, R->d, nullptr, nullptr, nullptr, nullptr);
+  launch_assembly(q, SO3_OBJECTIVE, grid, R->d, nullptr, nullptr, nullptr, nullptr);
   MI_HIP(hipGetLastError());
   MI_TRY(model_objective_to_slot(q, grid, ctx->scalars + SLOT_MISC));
   double s = 0;
@@ -737,7 +740,7 @@ int mi_so3n_model(mi_so3n *q, const mi_vec *R, mi_vec *grad, mi_op **hess, mi_pr
   MI_REQUIRE(grad->n == 3 * q->N, "gradient must hold 3N doubles");
   touch(grad);
   mi_ctx *ctx = q->ctx;
-  if (q->is_trial(R)) {
+  if (q->trial.is(R)) {
     // R is the point mi_so3n_trial just evaluated: its model exists already
     // (the point of an Armijo trial is NOT one: only its gradient exists -- the full assembly below)
     std::swap(q->Dinv, q->Dinv_next);
@@ -746,11 +749,11 @@ int mi_so3n_model(mi_so3n *q, const mi_vec *R, mi_vec *grad, mi_op **hess, mi_pr
     q->bj.data = q->Dinv->d;
     MI_TRY(mi_vec_copy(grad, q->grad_next));
   } else {
-    launch_model(q, true, model_grid(q), R->d, grad->d, q->Dinv->d, q->Bblk, q->Dsl);
+    launch_assembly(q, SO3_MODEL, model_grid(q), R->d, grad->d, q->Dinv->d, q->Bblk, q->Dsl);
     MI_HIP(hipGetLastError());
   }
-  q->trial_R = nullptr;
-  q->armijo_R = nullptr;
+  q->trial.clear();
+  q->armijo.clear();
   q->R = R;
   q->R_serial = R->serial;
   if (hess) *hess = &q->hess;
@@ -777,7 +780,7 @@ int mi_so3n_retract(mi_so3n *q, const mi_vec *R, const mi_vec *xi, mi_vec *Y) {
 int mi_so3n_trial(mi_so3n *q, const mi_vec *R, const mi_vec *h, const mi_vec *g, int with_precon, mi_vec *R_trial,
                   double out[6]) {
   MI_REQUIRE(q && R && h && g && R_trial && out, "null argument");
-  MI_REQUIRE(q->R == R && q->R_serial == R->serial,
+  MI_REQUIRE(bound_to(q->R, q->R_serial, R),
              "mi_so3n_trial: the model is not bound to this R (call mi_so3n_model first)");
   MI_REQUIRE(R->n == 9 * q->N && R_trial->n == 9 * q->N && h->n == 3 * q->N && g->n == 3 * q->N, "dimension mismatch");
   MI_REQUIRE(R_trial->d != R->d, "the trial point must not alias the current one");
@@ -792,35 +795,19 @@ int mi_so3n_trial(mi_so3n *q, const mi_vec *R, const mi_vec *h, const mi_vec *g,
     MI_HIP(hipMalloc((void **)&q->Bblk_next, std::max<size_t>(1, q->padded * 9) * sizeof(double)));
     MI_HIP(hipMalloc((void **)&q->Dsl_next, q->nslices * 9 * 64 * sizeof(double)));
   }
-  q->trial_R = nullptr;
-  q->armijo_R = nullptr;  // (grad_next is about to be overwritten)
+  q->trial.clear();
+  q->armijo.clear();  // (grad_next is about to be overwritten)
   // (a) Hess h, then |h|^2, <g,h>, <h, Hess h> in one pass (as MI355::dot_batch does)
   MI_TRY(so3_apply(&q->hess, h, q->Hh));
   {
     const double *xs[3] = {h->d, g->d, h->d}, *ys[3] = {h->d, h->d, q->Hh->d};
     MI_TRY(dot_batch_to_slots(ctx, 3, xs, ys, N3, SLOT_MISC));
   }
-  // (b) R+ = R exp(hat h) (+ the quaternions of R+, the assembly's gather records: the bits k_so3_quat would give)
-  if (q->Rq) {
-    touch(R_trial);
-    hipLaunchKernelGGL(k_so3_retract<true>, dim3(grid_for(ctx, q->N, 1)), dim3(kBlock), 0, ctx->stream, q->N,
-                       (const double *)R->d, (const double *)h->d, R_trial->d, q->Rq);
-    MI_HIP(hipGetLastError());
-  } else {
-    MI_TRY(mi_so3n_retract(q, R, h, R_trial));
-  }
+  // (b) R+ = R exp(hat h)
+  MI_TRY(retract_trial(q, R, h, R_trial));
   // (c) + (d) the model at R+ into the second set of arrays, with f(R+) from the same pass (r05: the objective was an
-  // edge pass of its own, 61 us and 416 MB at the fabric) -- reduced exactly as mi_so3n_objective does
-  {
-    const int grid = model_grid(q);
-    launch_model(q, true, grid, R_trial->d, q->grad_next->d, q->Dinv_next->d, q->Bblk_next, q->Dsl_next, q->Rq != nullptr);
-    MI_HIP(hipGetLastError());
-    MI_TRY(model_objective_to_slot(q, grid, ctx->scalars + SLOT_MISC + 3));
-  }
-  {
-    const double *xs[1] = {q->grad_next->d}, *ys[1] = {q->grad_next->d};
-    MI_TRY(dot_batch_to_slots(ctx, 1, xs, ys, N3, SLOT_MISC + 4));
-  }
+  // edge pass of its own, 61 us and 416 MB at the fabric), and |grad f(R+)|^2
+  MI_TRY(trial_tail(q, SO3_MODEL, R_trial, q->Dinv_next->d, q->Bblk_next, q->Dsl_next, SLOT_MISC + 3, SLOT_MISC + 4));
   if (with_precon) {
     mi_precon *tmp = nullptr;
     MI_TRY(mi_precon_create_block3(ctx, q->Dinv_next, &tmp));
@@ -840,10 +827,7 @@ int mi_so3n_trial(mi_so3n *q, const mi_vec *R, const mi_vec *h, const mi_vec *g,
   out[3] = buf[2];
   out[4] = buf[4];
   out[5] = with_precon ? buf[5] : -1.0;
-  q->trial_R = R_trial;
-  q->trial_d = R_trial->d;
-  q->trial_serial = R_trial->serial;
-  q->trial_gen = gen_of(R_trial);
+  q->trial.set(R_trial);
   return MI_OK;
 }
 
@@ -861,13 +845,13 @@ int mi_so3n_gradient(mi_so3n *q, const mi_vec *R, mi_vec *grad) {
   SO3_REQUIRE_ARGS(q && R && grad);
   MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
   MI_REQUIRE(grad->ctx == q->ctx && grad->n == 3 * q->N, "gradient must hold 3N doubles");
-  if (q->is_armijo(R) || q->is_trial(R)) {
+  if (q->armijo.is(R) || q->trial.is(R)) {
     // the last Armijo trial (or, speculatively, the last trust-region trial) evaluated this very point: its gradient is
     // there.  Neither key is consumed: a following mi_so3n_model(R) still finds the speculative model of a TNT trial.
     return mi_vec_copy(grad, q->grad_next);
   }
   touch(grad);
-  launch_grad(q, model_grid(q), R->d, grad->d, false);
+  launch_assembly(q, SO3_GRAD, model_grid(q), R->d, grad->d, nullptr, nullptr, nullptr);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
@@ -884,38 +868,19 @@ int mi_so3n_armijo_trial(mi_so3n *q, const mi_vec *R, const mi_vec *g, double t,
   ctx->fusion.fused_trial_steps++;
   const size_t N3 = 3 * q->N;
   if (!q->grad_next) MI_TRY(mi_vec_create(ctx, N3, &q->grad_next));  // (none of the Hessian-sized _next arrays)
-  q->trial_R = nullptr;  // (grad_next is about to be overwritten: the speculative model loses its gradient)
-  q->armijo_R = nullptr;
-  // (a) h = -t g: the kernel of DeviceVector's `-t * g` (mi_vec_scale_to), then R+ = R exp(hat h) with the quaternions
-  // of R+, the gather records of the pass below (k_so3_retract<true>, as in mi_so3n_trial)
+  q->trial.clear();  // (grad_next is about to be overwritten: the speculative model loses its gradient)
+  q->armijo.clear();
+  // (a) h = -t g: the kernel of DeviceVector's `-t * g` (mi_vec_scale_to), then R+ = R exp(hat h)
   MI_TRY(mi_vec_scale_to(h_out, -t, g));
-  if (q->Rq) {
-    touch(R_trial);
-    hipLaunchKernelGGL(k_so3_retract<true>, dim3(grid_for(ctx, q->N, 1)), dim3(kBlock), 0, ctx->stream, q->N,
-                       (const double *)R->d, (const double *)h_out->d, R_trial->d, q->Rq);
-    MI_HIP(hipGetLastError());
-  } else {
-    MI_TRY(mi_so3n_retract(q, R, h_out, R_trial));
-  }
-  // (b) grad f(R+) with the partials of f(R+) from the same pass, reduced exactly as mi_so3n_objective does
-  const int grid = model_grid(q);
-  launch_grad(q, grid, R_trial->d, q->grad_next->d, q->Rq != nullptr);
-  MI_HIP(hipGetLastError());
-  MI_TRY(model_objective_to_slot(q, grid, ctx->scalars + SLOT_MISC));
-  // (c) |grad f(R+)|^2 as metric(g, g) forms it (mi_vec_dot)
-  {
-    const double *xs[1] = {q->grad_next->d}, *ys[1] = {q->grad_next->d};
-    MI_TRY(dot_batch_to_slots(ctx, 1, xs, ys, N3, SLOT_MISC + 1));
-  }
+  MI_TRY(retract_trial(q, R, h_out, R_trial));
+  // (b) + (c) grad f(R+) with f(R+) from the same pass, and |grad f(R+)|^2
+  MI_TRY(trial_tail(q, SO3_GRAD, R_trial, nullptr, nullptr, nullptr, SLOT_MISC, SLOT_MISC + 1));
   // (d) one read-back
   double buf[2];
   MI_TRY(read_slots_sync(ctx, SLOT_MISC, 2, buf));
   out[0] = .25 * buf[0];  // (every edge from both ends)
   out[1] = buf[1];
-  q->armijo_R = R_trial;
-  q->armijo_d = R_trial->d;
-  q->armijo_serial = R_trial->serial;
-  q->armijo_gen = gen_of(R_trial);
+  q->armijo.set(R_trial);
   return MI_OK;
 }
 

@@ -1261,27 +1261,13 @@ struct mi_stiefel_rq {
   mi_dirgram dg;
   mi_op hess;     // borrowed operator object bound to X
   const mi_vec *X;
-  uint64_t X_serial = 0;  // (handles are recycled: "bound to this X" means this handle AND this vector's serial)
-  bool bound_to(const mi_vec *x) const { return X == x && x && X_serial == x->serial; }
+  uint64_t X_serial = 0;  // ("bound to this X": mi::bound_to(X, X_serial, .))
   // mi_stiefel_rq_trial: what it already worked out at the trial point (A X+, sym(X+'A X+), the gradient), handed
-  // to the next mi_stiefel_rq_model call if that call is for the same vector
+  // to the next mi_stiefel_rq_model call if that call is for the same vector with the same contents
   double *S_next = nullptr;
   mi_vec *Y_next = nullptr, *grad_next = nullptr, *Hh = nullptr;
-  // The cache key is the trial vector's handle AND its contents' identity (mi_vec::serial / gen): handles and pooled
-  // device pointers are both recycled, and an in-place write must invalidate the speculation too.
-  const mi_vec *trial_X = nullptr;
-  const double *trial_d = nullptr;
-  uint64_t trial_serial = 0, trial_gen = 0;
+  VecKey trial;
   bool warned_unsymmetric = false;
-  void remember_trial(const mi_vec *Xt) {
-    trial_X = Xt;
-    trial_d = Xt->d;
-    trial_serial = Xt->serial;
-    trial_gen = gen_of(Xt);
-  }
-  bool is_trial(const mi_vec *X) const {
-    return trial_X == X && trial_d == X->d && trial_serial == X->serial && trial_gen == gen_of(X);
-  }
 };
 
 namespace {
@@ -1554,6 +1540,63 @@ double tall_half_trace(const double *G, int p) {
   for (int a = 0; a < p; ++a) tr += G[a * 16 + a];
   return .5 * tr;
 }
+// ... that row (kTallTile doubles) and, if k > 0, slots [SLOT_MISC, SLOT_MISC + k) behind ONE host synchronisation
+int read_tall_row(mi_ctx *ctx, double *G, int k, double *misc) {
+  const void *dev[2] = {tall_reduced_row(ctx), ctx->scalars + SLOT_MISC};
+  const size_t bytes[2] = {kTallTile * sizeof(double), (size_t)k * sizeof(double)};
+  void *host[2] = {G, misc};
+  return readback_sync(ctx, k > 0 ? 2 : 1, dev, bytes, host);
+}
+// The objective .5 tr(sym(X'AX)) of the Gram rows just reduced and, behind the same single host synchronisation, the
+// k <= 4 slots [SLOT_MISC, SLOT_MISC + k).  Narrow rows: the packed symmetric Gram sits in the slots from SLOT_GRAM
+// (reduce_rows_allreduce) and ONE contiguous range is read, up to the last slot asked for; rows of 9 ... 16 doubles: 136
+// packed entries do not fit those slots, the reduced row (tall_reduce) is read back itself.
+int read_objective(mi_ctx *ctx, int p, double *f, int k, double *misc) {
+  if (tall_p(p)) {
+    double Gt[kTallTile];
+    MI_TRY(read_tall_row(ctx, Gt, k, misc));
+    *f = tall_half_trace(Gt, p);
+    return MI_OK;
+  }
+  static_assert(SLOT_GRAM < SLOT_MISC && SLOT_MISC + 4 <= kScalarSlots, "slot map");
+  double buf[SLOT_MISC + 4 - SLOT_GRAM];
+  MI_TRY(read_slots_sync(ctx, SLOT_GRAM, k > 0 ? SLOT_MISC + k - SLOT_GRAM : nsym(p), buf));
+  double tr = 0;
+  for (int a = 0, idx = 0; a < p; ++a) {  // diagonal entries of the packed symmetric Gram
+    tr += buf[idx];
+    idx += p - a;
+  }
+  *f = .5 * tr;
+  for (int i = 0; i < k; ++i) misc[i] = buf[SLOT_MISC - SLOT_GRAM + i];
+  return MI_OK;
+}
+
+// What mi_stiefel_rq_trial and mi_stiefel_rq_armijo_trial do once the trial point exists: A X+ with the Gram rows of
+// sym(X+'A X+) -- the objective, reduced exactly as mi_stiefel_rq_objective does, and through the same rows S+ and the
+// gradient at X+, exactly as mi_stiefel_rq_model does -- then |grad f(X+)|^2 into slot SLOT_MISC + k - 1 and the ONE
+// read-back: out[0] = f(X+), out[1 ... k] = slots [SLOT_MISC, SLOT_MISC + k).  Leaves q->trial set to X+.
+int rq_trial_chain(mi_stiefel_rq *q, const mi_vec *X_trial, int k, double *out) {
+  mi_ctx *ctx = q->ctx;
+  const size_t N = q->n * (size_t)q->p;
+  if (!q->Y_next) {
+    MI_TRY(mi_vec_create(ctx, N, &q->Y_next));
+    MI_TRY(mi_vec_create(ctx, N, &q->grad_next));
+    MI_HIP(hipMalloc((void **)&q->S_next, kMaxPTall * kMaxPTall * sizeof(double)));
+  }
+  int count = 0;
+  MI_TRY(launch_spmm_gram(ctx, q->A, q->p, nullptr, X_trial->d, X_trial->d, nullptr, q->Y_next->d, &count));
+  const bool tall = tall_p(q->p);
+  // (rows of 9 ... 16 doubles: the Gram rows are reduced once, into the row the finish pass and the read-back share)
+  if (tall) MI_TRY(tall_reduce(ctx, count));
+  else MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, nsym(q->p), ctx->scalars + SLOT_GRAM));
+  MI_TRY(launch_finish(ctx, q->n, q->p, nullptr, X_trial->d, q->Y_next->d, nullptr, tall ? 0 : count, q->S_next,
+                       q->grad_next->d, false, nullptr));
+  const double *gn[1] = {q->grad_next->d};
+  MI_TRY(dot_batch_to_slots(ctx, 1, gn, gn, N, SLOT_MISC + k - 1));
+  MI_TRY(read_objective(ctx, q->p, &out[0], k, out + 1));
+  q->trial.set(X_trial);
+  return MI_OK;
+}
 
 struct RqPreconImpl {
   mi_stiefel_rq *q;
@@ -1613,10 +1656,7 @@ int mi_stiefel_gram(mi_ctx *ctx, size_t n, int p, const mi_vec *X, const mi_vec 
     MI_TRY(tall_gram(ctx, n, p, 0, false, X->d, Z->d, nullptr, nullptr, &count));
     MI_TRY(tall_reduce(ctx, count));
     double G[kTallTile];
-    const void *dev[1] = {tall_reduced_row(ctx)};
-    const size_t bytes[1] = {sizeof(G)};
-    void *host[1] = {G};
-    MI_TRY(readback_sync(ctx, 1, dev, bytes, host));
+    MI_TRY(read_tall_row(ctx, G, 0, nullptr));
     for (int a = 0; a < p; ++a)
       for (int b = 0; b < p; ++b) G_host[a * p + b] = G[a * 16 + b];
     return MI_OK;
@@ -1717,31 +1757,12 @@ int mi_stiefel_rq_objective(mi_stiefel_rq *q, const mi_vec *X, double *f) {
   MI_REQUIRE(q && X && f, "null argument");
   MI_TRY(check_np(q->ctx, q->n, q->p, X, nullptr, nullptr));
   mi_ctx *ctx = q->ctx;
-  q->trial_X = nullptr;  // (Z is scratch of both)
+  q->trial.clear();  // (Z is scratch of both)
   int count = 0;
   MI_TRY(launch_spmm_gram(ctx, q->A, q->p, nullptr, X->d, X->d, nullptr, q->Z->d, &count));
-  if (tall_p(q->p)) {  // 136 packed entries do not fit the slots of SLOT_GRAM: the reduced row is read back itself
-    MI_TRY(tall_reduce(ctx, count));
-    double Gt[kTallTile];
-    const void *dev[1] = {tall_reduced_row(ctx)};
-    const size_t bytes[1] = {sizeof(Gt)};
-    void *host[1] = {Gt};
-    MI_TRY(readback_sync(ctx, 1, dev, bytes, host));
-    *f = tall_half_trace(Gt, q->p);
-    return MI_OK;
-  }
-  double *slots = ctx->scalars + SLOT_GRAM;
-  const int ns = nsym(q->p);
-  MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, ns, slots));
-  double G[kMaxP * (kMaxP + 1) / 2];
-  MI_TRY(read_slots_sync(ctx, SLOT_GRAM, ns, G));
-  double tr = 0;
-  for (int a = 0, idx = 0; a < q->p; ++a) {  // diagonal entries of the packed symmetric Gram
-    tr += G[idx];
-    idx += q->p - a;
-  }
-  *f = .5 * tr;
-  return MI_OK;
+  if (tall_p(q->p)) MI_TRY(tall_reduce(ctx, count));
+  else MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, nsym(q->p), ctx->scalars + SLOT_GRAM));
+  return read_objective(ctx, q->p, f, 0, nullptr);
 }
 
 int mi_stiefel_rq_model(mi_stiefel_rq *q, const mi_vec *X, mi_vec *grad, mi_op **hess) {
@@ -1749,7 +1770,7 @@ int mi_stiefel_rq_model(mi_stiefel_rq *q, const mi_vec *X, mi_vec *grad, mi_op *
   MI_TRY(check_np(q->ctx, q->n, q->p, X, grad, nullptr));
   int count = 0;
   touch(grad);
-  if (q->is_trial(X)) {
+  if (q->trial.is(X)) {
     // X is the point mi_stiefel_rq_trial just evaluated: A X, S and the gradient exist already
     std::swap(q->Y, q->Y_next);
     std::swap(q->S_dev, q->S_next);
@@ -1761,7 +1782,7 @@ int mi_stiefel_rq_model(mi_stiefel_rq *q, const mi_vec *X, mi_vec *grad, mi_op *
     MI_TRY(launch_finish(q->ctx, q->n, q->p, nullptr, X->d, q->Y->d, nullptr, count, q->S_dev, grad->d, false,
                          nullptr));
   }
-  q->trial_X = nullptr;
+  q->trial.clear();
   q->X = X;
   q->X_serial = X->serial;
   q->dg.p = q->p;
@@ -1796,19 +1817,15 @@ int mi_stiefel_rq_model(mi_stiefel_rq *q, const mi_vec *X, mi_vec *grad, mi_op *
 int mi_stiefel_rq_trial(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *h, const mi_vec *g, mi_vec *X_trial,
                         double out[5]) {
   MI_REQUIRE(q && X && h && g && X_trial && out, "null argument");
-  MI_REQUIRE(q->bound_to(X), "mi_stiefel_rq_trial: the model is not bound to this X (call mi_stiefel_rq_model first)");
+  MI_REQUIRE(bound_to(q->X, q->X_serial, X),
+             "mi_stiefel_rq_trial: the model is not bound to this X (call mi_stiefel_rq_model first)");
   MI_TRY(check_np(q->ctx, q->n, q->p, X, h, g));
   MI_TRY(check_np(q->ctx, q->n, q->p, X_trial, nullptr, nullptr));
   mi_ctx *ctx = q->ctx;
   ctx->fusion.fused_trial_steps++;
   const size_t N = q->n * (size_t)q->p;
-  if (!q->Y_next) {
-    MI_TRY(mi_vec_create(ctx, N, &q->Y_next));
-    MI_TRY(mi_vec_create(ctx, N, &q->grad_next));
-    MI_TRY(mi_vec_create(ctx, N, &q->Hh));
-    MI_HIP(hipMalloc((void **)&q->S_next, kMaxPTall * kMaxPTall * sizeof(double)));
-  }
-  q->trial_X = nullptr;
+  if (!q->Hh) MI_TRY(mi_vec_create(ctx, N, &q->Hh));
+  q->trial.clear();
   // (a) Hess h, then |h|^2, <g,h>, <h, Hess h> in one pass (as MI355::dot_batch does)
   MI_TRY(rq_apply(&q->hess, h, q->Hh));
   {
@@ -1817,48 +1834,8 @@ int mi_stiefel_rq_trial(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *h, cons
   }
   // (b) X+ = polar(X + h)
   MI_TRY(mi_stiefel_retract(ctx, q->n, q->p, X, h, X_trial));
-  // (c) A X+ with the Gram rows of sym(X+' A X+): the objective (reduced exactly as mi_stiefel_rq_objective does)
-  //     and, through the same rows, S+ and the gradient at X+ (exactly as mi_stiefel_rq_model does)
-  int count = 0;
-  MI_TRY(launch_spmm_gram(ctx, q->A, q->p, nullptr, X_trial->d, X_trial->d, nullptr, q->Y_next->d, &count));
-  const int ns = nsym(q->p);
-  const bool tall = tall_p(q->p);
-  // (rows of 9 ... 16 doubles: the Gram rows are reduced once, into the row the finish pass and the read-back share)
-  if (tall) MI_TRY(tall_reduce(ctx, count));
-  else MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, ns, ctx->scalars + SLOT_GRAM));
-  MI_TRY(launch_finish(ctx, q->n, q->p, nullptr, X_trial->d, q->Y_next->d, nullptr, tall ? 0 : count, q->S_next,
-                       q->grad_next->d, false, nullptr));
-  {
-    const double *xs[1] = {q->grad_next->d}, *ys[1] = {q->grad_next->d};
-    MI_TRY(dot_batch_to_slots(ctx, 1, xs, ys, N, SLOT_MISC + 3));
-  }
-  if (tall) {  // (d) one read-back: the reduced Gram row and slots [SLOT_MISC, SLOT_MISC + 4)
-    double Gt[kTallTile], misc[4];
-    const void *dev[2] = {tall_reduced_row(ctx), ctx->scalars + SLOT_MISC};
-    const size_t bytes[2] = {sizeof(Gt), sizeof(misc)};
-    void *host[2] = {Gt, misc};
-    MI_TRY(readback_sync(ctx, 2, dev, bytes, host));
-    out[0] = tall_half_trace(Gt, q->p);
-    for (int i = 0; i < 4; ++i) out[1 + i] = misc[i];
-    q->remember_trial(X_trial);
-    return MI_OK;
-  }
-  // (d) one read-back: slots [SLOT_GRAM, SLOT_MISC + 4)
-  static_assert(SLOT_GRAM < SLOT_MISC && SLOT_MISC + 4 <= kScalarSlots, "slot map");
-  double buf[SLOT_MISC + 4 - SLOT_GRAM];
-  MI_TRY(read_slots_sync(ctx, SLOT_GRAM, SLOT_MISC + 4 - SLOT_GRAM, buf));
-  double tr = 0;
-  for (int a = 0, idx = 0; a < q->p; ++a) {  // diagonal entries of the packed symmetric Gram
-    tr += buf[idx];
-    idx += q->p - a;
-  }
-  out[0] = .5 * tr;
-  out[1] = buf[SLOT_MISC - SLOT_GRAM + 0];
-  out[2] = buf[SLOT_MISC - SLOT_GRAM + 1];
-  out[3] = buf[SLOT_MISC - SLOT_GRAM + 2];
-  out[4] = buf[SLOT_MISC - SLOT_GRAM + 3];
-  q->remember_trial(X_trial);
-  return MI_OK;
+  // (c) f(X+), the model at X+ and |grad f(X+)|^2 behind the three dots; (d) one read-back
+  return rq_trial_chain(q, X_trial, 4, out);
 }
 
 // One Armijo trial of a backtracking line search along -g (reference Riemannian/GradientDescent.h:266-286:
@@ -1868,57 +1845,17 @@ int mi_stiefel_rq_trial(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *h, cons
 int mi_stiefel_rq_armijo_trial(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *g, double t, mi_vec *h_out,
                                mi_vec *X_trial, double out[2]) {
   MI_REQUIRE(q && X && g && h_out && X_trial && out, "null argument");
-  MI_REQUIRE(q->bound_to(X),
+  MI_REQUIRE(bound_to(q->X, q->X_serial, X),
              "mi_stiefel_rq_armijo_trial: the model is not bound to this X (call mi_stiefel_rq_model first)");
   MI_TRY(check_np(q->ctx, q->n, q->p, X, g, h_out));
   MI_TRY(check_np(q->ctx, q->n, q->p, X_trial, nullptr, nullptr));
   mi_ctx *ctx = q->ctx;
   ctx->fusion.fused_trial_steps++;
-  const size_t N = q->n * (size_t)q->p;
-  if (!q->Y_next) {
-    MI_TRY(mi_vec_create(ctx, N, &q->Y_next));
-    MI_TRY(mi_vec_create(ctx, N, &q->grad_next));
-    MI_TRY(mi_vec_create(ctx, N, &q->Hh));
-    MI_HIP(hipMalloc((void **)&q->S_next, kMaxPTall * kMaxPTall * sizeof(double)));
-  }
-  q->trial_X = nullptr;
+  q->trial.clear();
   touch(X_trial);
   MI_TRY(mi_vec_scale_to(h_out, -t, g));  // h = -t * g (:276)
   MI_TRY(mi_stiefel_retract(ctx, q->n, q->p, X, h_out, X_trial));
-  int count = 0;
-  MI_TRY(launch_spmm_gram(ctx, q->A, q->p, nullptr, X_trial->d, X_trial->d, nullptr, q->Y_next->d, &count));
-  const int ns = nsym(q->p);
-  const bool tall = tall_p(q->p);
-  if (tall) MI_TRY(tall_reduce(ctx, count));
-  else MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, count, ns, ctx->scalars + SLOT_GRAM));
-  MI_TRY(launch_finish(ctx, q->n, q->p, nullptr, X_trial->d, q->Y_next->d, nullptr, tall ? 0 : count, q->S_next,
-                       q->grad_next->d, false, nullptr));
-  {
-    const double *xs[1] = {q->grad_next->d}, *ys[1] = {q->grad_next->d};
-    MI_TRY(dot_batch_to_slots(ctx, 1, xs, ys, N, SLOT_MISC));
-  }
-  if (tall) {  // one read-back: the reduced Gram row and slot SLOT_MISC
-    double Gt[kTallTile], misc[1];
-    const void *dev[2] = {tall_reduced_row(ctx), ctx->scalars + SLOT_MISC};
-    const size_t bytes[2] = {sizeof(Gt), sizeof(misc)};
-    void *host[2] = {Gt, misc};
-    MI_TRY(readback_sync(ctx, 2, dev, bytes, host));
-    out[0] = tall_half_trace(Gt, q->p);
-    out[1] = misc[0];
-    q->remember_trial(X_trial);
-    return MI_OK;
-  }
-  double buf[SLOT_MISC + 1 - SLOT_GRAM];
-  MI_TRY(read_slots_sync(ctx, SLOT_GRAM, SLOT_MISC + 1 - SLOT_GRAM, buf));
-  double tr = 0;
-  for (int a = 0, idx = 0; a < q->p; ++a) {
-    tr += buf[idx];
-    idx += q->p - a;
-  }
-  out[0] = .5 * tr;
-  out[1] = buf[SLOT_MISC - SLOT_GRAM];
-  q->remember_trial(X_trial);
-  return MI_OK;
+  return rq_trial_chain(q, X_trial, 1, out);
 }
 
 int mi_stiefel_rq_precon(mi_stiefel_rq *q, const mi_vec *X, const mi_vec *dinv_rows, mi_precon **out) {

@@ -26,6 +26,12 @@ PARENT_FIGURES = {
     "k_so3_retract<false>": (78, 64, 8, 0),
     "k_so3_retract<true>": (78, 60, 8, 0),
     "k_so3_quat": (26, 37, 8, 0),
+    # the gradient-only pass as commit 109fb61 compiles it (the figures of profiles/gd_so3n_ab.md): the last commit in
+    # which it had a body of its own, before k_so3_model and k_so3_grad became two entry names over one body
+    "k_so3_grad<false, false>": (44, 106, 4, 0),
+    "k_so3_grad<false, true>": (46, 106, 4, 0),
+    "k_so3_grad<true, false>": (44, 110, 4, 0),
+    "k_so3_grad<true, true>": (46, 110, 4, 0),
 }
 
 

@@ -518,6 +518,40 @@ def test_fused_trial_step_has_the_bits_of_the_separate_calls(ctx, p):
     assert np.array_equal(r1["s"].numpy(), r2["s"].numpy())
 
 
+@pytest.mark.parametrize("p", [1, 2, 3, 4, 5, 8])
+def test_fused_armijo_trial_has_the_bits_of_the_separate_calls(ctx, p):
+    """mi_stiefel_rq_armijo_trial on narrow rows (reference Riemannian/GradientDescent.h:266-286,325-327 as one launch
+    chain, one read-back) against the separate calls it replaces -- the step -t g, retraction, objective, gradient at the
+    trial point and its squared norm: bit for bit, as test_tall_rows_fused_trial_steps_have_the_bits_of_the_separate_calls
+    asks of p = 9 and 16."""
+    import ctypes as C
+    from optimization_amd import capi
+    nx, ny, nz = 20, 17, 13
+    n = nx * ny * nz
+    rowptr, col, val = wl.laplacian_3d(nx, ny, nz)
+    A = ctx.csr(n, rowptr, col, val)
+    prob, prob2 = ctx.stiefel_rq(A, n, p), ctx.stiefel_rq(A, n, p)
+    X = ctx.upload(wl.random_stiefel(n, p, seed=3))
+    g, _ = prob.model(X)
+    step = 1e-3
+    # separate calls (the model on a problem object of its own: nothing speculative to take)
+    hs = g.scaled(-step)
+    Xa_ref = ctx.stiefel_retract(n, p, X, hs)
+    fa_ref = prob2.objective(Xa_ref)
+    ga_ref, _ = prob2.model(Xa_ref)
+    # fused
+    h_out, Xa, out = capi.Vec(ctx, n * p), capi.Vec(ctx, n * p), np.zeros(2)
+    syncs = ctx.sync_count()
+    capi.check(ctx.L.mi_stiefel_rq_armijo_trial(prob.h, X.h, g.h, C.c_double(step), h_out.h, Xa.h,
+                                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+    assert ctx.sync_count() - syncs == 1
+    assert np.array_equal(h_out.numpy(), hs.numpy())
+    assert np.array_equal(Xa.numpy(), Xa_ref.numpy())
+    assert (out[0], out[1]) == (fa_ref, ga_ref.dot(ga_ref))
+    ga, _ = prob.model(Xa)           # takes A X+, S+ and the gradient from the trial call
+    assert np.array_equal(ga.numpy(), ga_ref.numpy())
+
+
 def test_speculative_trial_model_is_keyed_on_the_vector_contents(ctx):
     """mi_stiefel_rq_trial's cached A X+, S+, gradient must only serve a model() call for the SAME trial
     vector contents -- not an in-place overwritten one, not a new vector that recycled the handle / pooled pointer."""
