@@ -451,6 +451,23 @@ class Context:
         check(self.L.mi_op_create_callback(self.h, n, cfn, None, C.byref(h)))
         return Op(self, h, keep=[cfn])
 
+    def op_callback_rect(self, n_in, n_out, fn):
+        """mi_op_create_callback_rect: fn(in_vec: Vec of n_in, out_vec: Vec of n_out) enqueues out = Op(in)."""
+        def cb(_u, pin, pout):
+            try:
+                fn(Vec(self, 0, handle=vp(pin)), Vec(self, 0, handle=vp(pout)))
+                return 0
+            except Exception:  # noqa
+                import traceback
+                traceback.print_exc()
+                return 6
+        cfn = APPLY_FN(cb)
+        h = vp()
+        check(self.L.mi_op_create_callback_rect(self.h, n_in, n_out, cfn, None, C.byref(h)))
+        op = Op(self, h, keep=[cfn])
+        op.n_in = n_in
+        return op
+
     def op_callback_fused(self, n, fn, fused):
         """mi_op_create_callback_fused.  fn(in_vec, out_vec) enqueues out = Op(in); fused(in_vec, out_vec, args) does the
         same AND leaves the three curvature partial rows (args: FusedArgs), returning the number of rows written.  (A
@@ -606,7 +623,7 @@ class Context:
                 raise AttributeError(k)
             setattr(prm, k, v)
         res = LsqrResult()
-        x = x_out if x_out is not None else Vec(self, kw_nx if (kw_nx := getattr(A, "n_in", None)) else b.n)
+        x = x_out if x_out is not None else Vec(self, getattr(A, "n_in", None) or b.n)
         if observer is not None:
             raised = []
 

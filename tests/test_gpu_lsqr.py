@@ -32,7 +32,9 @@ def test_lsqr_solves_a_nonsymmetric_system(ctx):
     Aop, Atop = _ops(ctx, A)
     r = ctx.lsqr(Aop, Atop, ctx.upload(b), btol=1e-12, Atol=1e-12, max_iterations=500)
     x = r["x"].numpy()
-    assert r["exit_reason"] in (1, 2) and r["iterations"] < 500
+    # S1: what the restatement of the reference (tests/lsqr_reference.py) gives for this input in long double and in
+    # float64 under five orders of its sums -- S2's left side stays eleven orders above its right in every pass
+    assert r["exit_reason"] == 1 and r["iterations"] < 500
     assert np.abs(x - xs).max() < 1e-9
     assert abs(r["xnorm"] - np.linalg.norm(x)) <= 1e-9 * np.linalg.norm(x)      # the QR-based |x| estimate
     assert r["operator_applications"] >= 2 * r["iterations"] + 1
