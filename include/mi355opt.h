@@ -108,6 +108,9 @@ enum {
                           one exchange kernel of the peer-memory layer; folded exchanges have none */
   MI_K_COMM_HALO,      /* a halo exchange that is a launch of its own: ncclSend/ncclRecv group or push kernel */
   MI_K_SO3_GRAD,        /* the gradient-only assembly pass of mi_so3n_gradient / mi_so3n_armijo_trial */
+  MI_K_SO3_RESIDUAL,    /* k_so3_residual: F(R) of mi_so3n_residual */
+  MI_K_SO3_JAC,         /* k_so3_jac: dF xi over the edges (apply and apply_sub_scaled forms) */
+  MI_K_SO3_JACT,        /* k_so3_jact: dF* y over the incidences (apply and apply_sub_scaled forms) */
   MI_K_COUNT
 };
 /* The library's switches (A/B forms of its kernels, verification hooks of the multi-rank path) are read from the
@@ -504,6 +507,27 @@ MI_API int mi_so3n_gradient(mi_so3n *prob, const mi_vec *R, mi_vec *grad);
  * would produce. */
 MI_API int mi_so3n_armijo_trial(mi_so3n *prob, const mi_vec *R, const mi_vec *g, double t, mi_vec *h_out,
                                 mi_vec *R_trial, double out[2]);
+/* The same problem as a nonlinear least-squares one, f(R) = 1/2 |F(R)|^2 (Riemannian/TNLS.h: Mapping, JacobianPairFunction):
+ *   F(R)_e = sqrt(w_e) (R_j - R_i Rt_e), 9 doubles (row-major) per edge e = (i -> j) in the caller's edge order.
+ * Needs w >= 0.  mi_so3n_residual is the Mapping F of TNLS.h:265 (F(x) at :399 and F(x_trial) at :553); sqnorm_or_null
+ * receives |F(R)|^2 from the partial rows of the same pass (sync) -- null: no sync.  Reads R (or, at the point of the
+ * last fused trial step, its quaternion records) and writes nothing that a Jacobian handed out earlier reads. */
+MI_API int mi_so3n_residual(mi_so3n *prob, const mi_vec *R, mi_vec *F_out, double *sqnorm_or_null);
+/* The Jacobian pair of TNLS.h:269,414-426 at R, as the two operators of LSQR's bidiagonalisation
+ * (LinearAlgebra/IterativeSolvers.h:707 u = A v - alpha u, :712 v = A' u - beta v: both have apply_sub_scaled forms):
+ *   (dF xi)_e = sqrt(w_e) (R_j hat(xi_j) - R_i hat(xi_i) Rt_e)                                      3N -> 9E
+ *   (dF* Y)_i = sum over the incidences of node i, in their fixed slot order, of
+ *               -sqrt(w_e) vee(R_i' Y_e Rt_e')  where i is the first node of e,  +sqrt(w_e) vee(R_i' Y_e)  where the second
+ * with vee(M) = (M7 - M5, M2 - M6, M3 - M1).  No atomics: the same bits on every run.  Both handles are owned by the
+ * problem (borrowed) and rebound by every call; they read a copy of the rotations taken by this call, so R may be
+ * written, and the residual evaluated elsewhere, while they are in use.  dF has the 3-dimensional null space of the
+ * global rotation; LSQR returns the minimum-norm step.  n_edges = 0 is MI_ERR_INVALID_ARGUMENT.  The first call uploads
+ * the per-edge streams and the incidence -> edge map (sync); later calls do not synchronise. */
+MI_API int mi_so3n_jacobian(mi_so3n *prob, const mi_vec *R, mi_op **dF, mi_op **dFt);
+/* The right preconditioner pair (M, M') of TNLS.h:60-63 for this problem, M = M' = diag(1 / sqrt(2 degw_i)) (each entry
+ * three times; 1 for a node of weighted degree 0): the diagonal blocks of dF* dF are exactly 2 degw_i I (|R hat(xi) S|^2 =
+ * 2 |xi|^2), so this is the block-Jacobi scaling of the Gauss-Newton system.  Point-independent; owned by the problem. */
+MI_API int mi_so3n_gn_scaling(mi_so3n *prob, mi_op **M);
 
 /* ---------------------------------------------------------------------------------------------
  * (8) LOBPCG building blocks (LinearAlgebra/LOBPCG.h:131-337).  Panels are column-major m x k
@@ -641,6 +665,11 @@ MI_API int mi_debug_csr_format_info(const mi_csr *A, size_t out[5]);
 /* read-only: the forms an SO(3)^N problem took -- {measurements stored as unit quaternions, neighbours gathered as
  * quaternions, slices, incidences, padded incidence slots, workgroups of the model assembly}; needs no GPU work */
 MI_API int mi_debug_so3n_info(const mi_so3n *q, size_t out[6]);
+/* Test hook: one application of the operator's fused LSQR form (IterativeSolvers.h:707,712: inout = Op(in) - scale inout
+ * with |inout|^2 from the same pass) driven as mi_lsqr drives it; nothing happens when mode != 0.  MI_DECLINED when the
+ * operator has no such form.  sync. */
+MI_API int mi_debug_op_apply_sub_scaled(mi_op *op, const mi_vec *in, double scale, int mode, mi_vec *inout,
+                                        double *sqnorm);
 /* host-only: the run plan of the LDS-window kernels (first tile of every run + the end) for `ntiles` tiles of 256 rows,
  * a workgroup budget, a CU count and the matrix's far stride in rows (0: none); needs no GPU */
 MI_API int mi_debug_window_runs(int ntiles, int max_wgs, int num_cu, size_t far_stride, int *bounds_out, int cap,

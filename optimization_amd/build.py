@@ -141,7 +141,9 @@ def build_harness(force=False):
       tests/cpp/libharness_observer.so  STPCG with a user function on both vector types (one driver)
       tests/cpp/libharness_args.so    the optimizers called with an extra-argument pack (Args...), empty and not
       tests/cpp/libharness_lsqr_observer.so  LSQR with a user function: C ABI and template layer
-      tests/cpp/libharness_gd_so3n.so GradientDescent on MI355::RotationAveraging (fused Armijo trial and its controls)"""
+      tests/cpp/libharness_gd_so3n.so GradientDescent on MI355::RotationAveraging (fused Armijo trial and its controls)
+      tests/cpp/libharness_tnls_so3n.so TNLS on MI355::RotationAveraging as a least-squares problem: host restatement,
+                                      tagged device accessors, the same operators behind plain lambdas"""
     tdir = os.path.join(ROOT, "tests", "cpp")
     inc = ["-I", os.path.join(HERE, "include"), "-I", os.path.join(ROOT, "oracle")]
     common = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-type-limits"]
@@ -183,9 +185,9 @@ def build_harness(force=False):
         if r.returncode != 0:
             raise RuntimeError("observer harness build failed:\n" + r.stderr[-6000:])
     out.append(ob_so)
-    # tests/cpp/harness_args.cpp, harness_lsqr_observer.cpp, harness_gd_so3n.cpp: g++, and clang's front end on the same
+    # tests/cpp/harness_args.cpp, harness_lsqr_observer.cpp, harness_gd_so3n.cpp, harness_tnls_so3n.cpp: g++, and clang's front end on the same
     # translation units (the pack-carrying instantiations of the template layer must pass both)
-    for name in ("harness_args", "harness_lsqr_observer", "harness_gd_so3n"):
+    for name in ("harness_args", "harness_lsqr_observer", "harness_gd_so3n", "harness_tnls_so3n"):
         src = os.path.join(tdir, name + ".cpp")
         so = os.path.join(tdir, "lib" + name + ".so")
         if force or _newer(src, so, hdrs + [LIB]):

@@ -201,6 +201,9 @@ def load():
         "mi_so3n_trial": [vp, vp, vp, vp, C.c_int, vp, c_double_p],
         "mi_so3n_gradient": [vp, vp, vp],
         "mi_so3n_armijo_trial": [vp, vp, vp, C.c_double, vp, vp, c_double_p],
+        "mi_so3n_residual": [vp, vp, vp, c_double_p],
+        "mi_so3n_jacobian": [vp, vp, C.POINTER(vp), C.POINTER(vp)],
+        "mi_so3n_gn_scaling": [vp, C.POINTER(vp)],
         "mi_stpcg_collect": [vp, C.POINTER(StpcgResult)],
         "mi_lobpcg_gram": [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, c_double_p],
         "mi_lobpcg_update": [vp, C.c_size_t, C.c_int, C.c_int, vp, c_double_p, C.c_int, vp],
@@ -237,6 +240,7 @@ def load():
         "mi_debug_csr_window_info": [vp, c_size_p],
         "mi_debug_csr_format_info": [vp, c_size_p],
         "mi_debug_so3n_info": [vp, c_size_p],
+        "mi_debug_op_apply_sub_scaled": [vp, vp, C.c_double, C.c_int, vp, c_double_p],
         "mi_debug_time_fused_apply": [vp, vp, vp, C.c_int, c_double_p],
         "mi_debug_set_rank": [vp, C.c_int, C.c_int],
         "mi_debug_csr_set_halo": [vp, C.c_int, c_double_p],
@@ -1026,9 +1030,16 @@ class Op:
         self.ctx, self.L, self.h, self.keep, self.borrowed = ctx, ctx.L, h, list(keep), borrowed
 
     def apply(self, x, out=None):
-        out = out if out is not None else Vec(self.ctx, x.n)
+        out = out if out is not None else Vec(self.ctx, getattr(self, "n_out", None) or x.n)
         check(self.L.mi_op_apply(self.h, x.h, out.h))
         return out
+
+    def apply_sub_scaled(self, x, scale, inout, mode=0):
+        """mi_debug_op_apply_sub_scaled: inout = Op(x) - scale inout in the operator's fused LSQR form; returns |inout|^2
+        from the same pass (None when mode != 0: nothing must happen)"""
+        s = C.c_double(float("nan"))
+        check(self.L.mi_debug_op_apply_sub_scaled(self.h, x.h, float(scale), int(mode), inout.h, C.byref(s)))
+        return s.value if mode == 0 else None
 
     def time_fused_apply(self, x, out, reps=200):
         """average us per application in the fused form mi_stpcg uses (mi_debug_time_fused_apply)"""
@@ -1146,6 +1157,29 @@ class So3N:
         g = out if out is not None else Vec(self.ctx, 3 * self.N)
         check(self.L.mi_so3n_gradient(self.h, R.h, g.h))
         return g
+
+    def residual(self, R, out=None, sqnorm=False):
+        """mi_so3n_residual: F(R) (9E, sqrt(w_e) (R_j - R_i Rt_e) per edge); with sqnorm also |F|^2 of the same pass"""
+        F = out if out is not None else Vec(self.ctx, 9 * self.E)
+        s = C.c_double(0)
+        check(self.L.mi_so3n_residual(self.h, R.h, F.h, C.byref(s) if sqnorm else None))
+        return (F, s.value) if sqnorm else F
+
+    def jacobian(self, R):
+        """mi_so3n_jacobian: (dF Op 3N -> 9E, dF* Op 9E -> 3N), problem-owned, rebound by every call"""
+        a, at = vp(), vp()
+        check(self.L.mi_so3n_jacobian(self.h, R.h, C.byref(a), C.byref(at)))
+        dF, dFt = Op(self.ctx, a, keep=[self], borrowed=True), Op(self.ctx, at, keep=[self], borrowed=True)
+        dF.n_in, dF.n_out, dFt.n_in, dFt.n_out = 3 * self.N, 9 * self.E, 9 * self.E, 3 * self.N
+        return dF, dFt
+
+    def gn_scaling(self):
+        """mi_so3n_gn_scaling: the diagonal operator diag(1 / sqrt(2 degw_i)) (3N), problem-owned"""
+        m = vp()
+        check(self.L.mi_so3n_gn_scaling(self.h, C.byref(m)))
+        M = Op(self.ctx, m, keep=[self], borrowed=True)
+        M.n_in = M.n_out = 3 * self.N
+        return M
 
     def armijo_trial(self, R, g, t, h=None, R_trial=None):
         """mi_so3n_armijo_trial: (h = -t g Vec, R_trial Vec, dict(f, grad_sqnorm))"""

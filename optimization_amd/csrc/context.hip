@@ -353,7 +353,8 @@ static const char *kKernelNames[MI_K_COUNT] = {
     "none", "cg_init", "cg_dot3", "cg_scalar_a", "cg_update", "cg_scalar_b", "cg_pupdate",
     "csr_spmm", "stiefel_spmm_gram", "stiefel_gram_reduce", "stiefel_finish_dots",
     "stiefel_retract", "bsr3_spmv_dots", "blas1", "lobpcg_gram", "lobpcg_update",
-    "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo", "so3_grad"};
+    "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo", "so3_grad",
+    "so3_residual", "so3_jac", "so3_jact"};
 const char *mi_kernel_name(int id) {
   if (id < 0 || id >= MI_K_COUNT) return "?";
   return kKernelNames[id];

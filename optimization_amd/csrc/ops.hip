@@ -296,6 +296,34 @@ int mi_debug_time_fused_apply(mi_op *op, const mi_vec *in, mi_vec *out, int reps
   return MI_OK;
 }
 
+// Test hook (tests/test_gpu_so3n_nls.py): ONE application of the operator's apply_sub_scaled form the way mi_lsqr drives
+// it -- scale and mode in device memory, the partial rows in ctx->partials -- inout = Op(in) - scale inout, and
+// *sqnorm = the sum of the partial rows of |inout|^2 (untouched, like inout, when mode != 0: the kernel must do nothing).
+// MI_DECLINED: the operator has no such form.
+int mi_debug_op_apply_sub_scaled(mi_op *op, const mi_vec *in, double scale, int mode, mi_vec *inout, double *sqnorm) {
+  MI_REQUIRE(op && in && inout && sqnorm, "null argument");
+  MI_REQUIRE(in->n == op->n && inout->n == (op->n_out ? op->n_out : op->n), "operator dimension mismatch");
+  if (!op->apply_sub_scaled) return MI_DECLINED;
+  mi_ctx *ctx = op->ctx;
+  void *raw = nullptr;
+  MI_TRY(pool_alloc(ctx, 64, &raw));
+  struct { double scale; int mode, gate; } host = {scale, mode, 1};
+  int ret = stage_upload(ctx, &host, sizeof(host), raw);
+  int nparts = 0;
+  touch(inout);
+  if (ret == MI_OK)
+    ret = op->apply_sub_scaled(op, in, (const double *)raw, (const int *)((const char *)raw + 8),
+                               (const int *)((const char *)raw + 12), inout, ctx->partials, &nparts);
+  if (ret == MI_OK && mode == 0) {
+    ret = reduce_rows_allreduce(ctx, ctx->partials, nparts, 1, ctx->scalars + SLOT_MISC);
+    if (ret == MI_OK) ret = read_slots_sync(ctx, SLOT_MISC, 1, sqnorm);
+  } else if (ret == MI_OK) {
+    ret = stream_wait(ctx, "mi_debug_op_apply_sub_scaled");
+  }
+  pool_free(ctx, raw);
+  return ret;
+}
+
 int mi_op_dims(const mi_op *op, size_t *n_in, size_t *n_out) {
   MI_REQUIRE(op, "op is null");
   if (n_in) *n_in = op->n;

@@ -17,6 +17,26 @@
 // ((slice_ptr[s] + k) * 9 + c) * 64 + lane  => each of the 9 component streams is coalesced; the
 // diagonal blocks D_i are kept in the same slice order (Dsl).
 // Algorithmic bytes per HVP: 72 (nnzb + N) + 4 nnzb + 8 (3N read + 3N written)  [nnzb = incidences].
+//
+// The same problem as a nonlinear least-squares one for TNLS / LSQR (mi_so3n_residual, mi_so3n_jacobian):
+//     F(R)_e = sqrt(w_e) (R_j - R_i Rt_e)  in R^{9E},   f = 1/2 |F|^2,   dF* F = grad f
+//     (dF xi)_e = sqrt(w_e) (R_j hat(xi_j) - R_i hat(xi_i) Rt_e)
+//     (dF* Y)_i = sum_{incidences of i, slot order} -sqrt(w_e) vee(R_i' Y_e Rt_e') [i first node of e] / +sqrt(w_e) vee(R_i' Y_e)
+// F and dF walk the EDGES in the caller's order (one thread per edge: per-edge streams of the end points, sqrt(w) and the
+// measurement -- a quaternion when the problem is SQ), dF* walks the node-centric SELL incidence layout above (one lane per
+// node, its incidences summed in slot order: no atomics) with one 4-byte word per slot, edge << 1 | (node is the first
+// node of the edge); the measurement a first node needs, Rt_e', is what Sinc holds for that slot already.
+// How the rotations reach the Jacobian kernels: RANDOM GATHERS from a buffer of the Jacobian's own (Jrot), written once per
+// linearisation -- the 32-byte quaternion records copied from Rq when they are valid for the point (mi_so3n::rq), else
+// the 72-byte rows copied from R.  A per-edge stream of both end rotations would be 64 (144) coalesced bytes per edge per
+// application from HBM, written as 2E records per linearisation; the node buffer is 32 N bytes (16 MB at N = 5e5) that the
+// 2E gathers of a pass re-visit out of L2 / MALL, and dF* needs only the lane's own rotation.  The buffer is also what keeps
+// the operators valid while TNLS evaluates F at trial points: nothing else writes it.
+// Algorithmic bytes per application [quaternion forms; (matrix forms)], E edges, nnzb = 2E:
+//     F      16 E (end points, sqrt w) + 32 (72) E measurement + 64 (144) E rotations + 72 E written           = 184 (304) E
+//     dF     the same reads + 48 E (xi_i, xi_j) + 72 E written [+ 72 E read: apply_sub_scaled]                  = 232 (352) E [+ 72 E]
+//     dF*    nnzb (8 weight + 4 word + 72 Y_e) + 32 (72) E measurement at first nodes + N (4 + 32 (72) + 24 written [+ 24])
+//                                                                                                               = 200 (240) E + 60 (100) N [+ 24 N]
 #include <algorithm>
 
 #include "mi_internal.h"
@@ -33,7 +53,15 @@ struct IncView {
   const int *__restrict__ perm;   // node owned by (slice, lane), -1 for the padding lanes of the last window
   const int *__restrict__ nbr;    // neighbour node j (padding: own node)
   // (padding entries carry weight 0 in winc, which is what the kernels test: the edge ids and the head/tail flags the
-  // packing uses stay on the host, 4 + 1 bytes per incidence entry nobody streams)
+  // packing uses stay on the host, 4 + 1 bytes per incidence entry nobody streams -- until the Jacobian is first asked
+  // for: mi_so3n::slot_edge, k_so3_jact)
+};
+// the edges in the caller's order (mi_so3n_residual, mi_so3n_jacobian; uploaded on first use)
+struct EdgeView {
+  size_t E;
+  const int2 *__restrict__ ij;     // (i, j) of e = (i -> j)
+  const double *__restrict__ Se;   // measurement Rt_e, component-major: component c of edge e at c * E + e (4 or 9 components)
+  const double *__restrict__ sw;   // sqrt(w_e)
 };
 
 __device__ __forceinline__ void mat3_mul(const double *A, const double *B, double *C) {
@@ -397,6 +425,172 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(80))) void k
   }
 }
 
+// ---- nonlinear least-squares view: F, dF, dF* (see the file header) ---------------------------------------------------
+// rotation `i` of a node buffer: GQ -- 32-byte unit quaternion records (Rq layout), else 72-byte row-major rows
+template <bool GQ>
+__device__ __forceinline__ void load_rot(const double *__restrict__ rot, size_t i, double *Ri) {
+  if (GQ) {
+    const double2 qa = *reinterpret_cast<const double2 *>(rot + 4 * i), qb = *reinterpret_cast<const double2 *>(rot + 4 * i + 2);
+    quat_to_mat(qa.x, qa.y, qb.x, qb.y, Ri);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 9; ++c) Ri[c] = rot[9 * i + c];
+  }
+}
+template <bool SQ>
+__device__ __forceinline__ void load_edge_meas(const EdgeView &ev, size_t e, double *S) {
+  if (SQ) {
+    quat_to_mat(ev.Se[e], ev.Se[ev.E + e], ev.Se[2 * ev.E + e], ev.Se[3 * ev.E + e], S);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 9; ++c) S[c] = ev.Se[(size_t)c * ev.E + e];
+  }
+}
+// M = Q hat(x): row r of Q crossed with x
+__device__ __forceinline__ void q_hat(const double *Q, double x0, double x1, double x2, double *M) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double q0 = Q[r * 3], q1 = Q[r * 3 + 1], q2 = Q[r * 3 + 2];
+    M[r * 3] = q1 * x2 - q2 * x1;
+    M[r * 3 + 1] = q2 * x0 - q0 * x2;
+    M[r * 3 + 2] = q0 * x1 - q1 * x0;
+  }
+}
+constexpr int kNlsBlock = 256;  // one thread per edge / per node lane, <= kMaxRows workgroups (grid-stride beyond): one
+                                // partial row of the squared norm per workgroup, component 0
+// F_e = sqrt(w_e) (R_j - R_i Rt_e) ; partial |F|^2
+template <bool SQ, bool GQ>
+__global__ __launch_bounds__(kNlsBlock) void k_so3_residual(EdgeView ev, const double *__restrict__ rot,
+                                                            double *__restrict__ F, double *__restrict__ partials) {
+  __shared__ double lds[4];
+  double acc[1] = {0};
+  const size_t stride = (size_t)gridDim.x * kNlsBlock;
+  for (size_t e = (size_t)blockIdx.x * kNlsBlock + threadIdx.x; e < ev.E; e += stride) {
+    const int2 ij = ev.ij[e];
+    const double sw = ev.sw[e];
+    double Ri[9], Rj[9], S[9], RiS[9];
+    load_rot<GQ>(rot, (size_t)ij.x, Ri);
+    load_rot<GQ>(rot, (size_t)ij.y, Rj);
+    load_edge_meas<SQ>(ev, e, S);
+    mat3_mul(Ri, S, RiS);
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+      const double f = sw * (Rj[c] - RiS[c]);
+      F[9 * e + c] = f;
+      acc[0] += f * f;
+    }
+  }
+  block_partials_store_nw<1, kNlsBlock / 64>(acc, lds, partials);
+}
+// y_e = sqrt(w_e) (R_j hat(xi_j) - R_i hat(xi_i) Rt_e).  FUSED (mi_op::apply_sub_scaled, IterativeSolvers.h:707):
+// y_e = that - (*scale) y_e with the partial rows of |y|^2; nothing when *mode != 0 or (gate && !*gate).
+template <bool FUSED, bool SQ, bool GQ>
+__global__ __launch_bounds__(kNlsBlock) void k_so3_jac(EdgeView ev, const double *__restrict__ rot,
+                                                       const double *__restrict__ xi, double *__restrict__ y,
+                                                       const double *__restrict__ scale, const int *__restrict__ mode,
+                                                       const int *__restrict__ gate, double *__restrict__ partials) {
+  __shared__ double lds[4];
+  double alpha = 0;
+  if (FUSED) {
+    if (*mode != 0 || (gate && !*gate)) return;
+    alpha = *scale;
+  }
+  double acc[1] = {0};
+  const size_t stride = (size_t)gridDim.x * kNlsBlock;
+  for (size_t e = (size_t)blockIdx.x * kNlsBlock + threadIdx.x; e < ev.E; e += stride) {
+    const int2 ij = ev.ij[e];
+    const size_t i = (size_t)ij.x, j = (size_t)ij.y;
+    const double sw = ev.sw[e];
+    double Ri[9], Rj[9], S[9], A[9], B[9], BS[9];
+    load_rot<GQ>(rot, i, Ri);
+    load_rot<GQ>(rot, j, Rj);
+    load_edge_meas<SQ>(ev, e, S);
+    q_hat(Rj, xi[3 * j], xi[3 * j + 1], xi[3 * j + 2], A);
+    q_hat(Ri, xi[3 * i], xi[3 * i + 1], xi[3 * i + 2], B);
+    mat3_mul(B, S, BS);
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+      double t = sw * (A[c] - BS[c]);
+      if (FUSED) {
+        t = t - alpha * y[9 * e + c];
+        acc[0] += t * t;
+      }
+      y[9 * e + c] = t;
+    }
+  }
+  if (FUSED) block_partials_store_nw<1, kNlsBlock / 64>(acc, lds, partials);
+}
+// x_i = vee(R_i' G_i),  G_i = sum over the incidence slots of node i, in slot order, of  -sqrt(w) Y_e Rt_e'  (i the first
+// node of e; Rt_e' = the slot's Sinc) or +sqrt(w) Y_e (the second).  One lane per node, 4 slices per workgroup, the walk of
+// k_so3_model.  FUSED (IterativeSolvers.h:712): x_i = that - (*scale) x_i with the partial rows of |x|^2, gated as above.
+template <bool FUSED, bool SQ, bool GQ>
+__global__ __launch_bounds__(kNlsBlock) void k_so3_jact(IncView inc, const double *__restrict__ rot,
+                                                        const double *__restrict__ Sinc, const double *__restrict__ winc,
+                                                        const uint32_t *__restrict__ slot_edge,
+                                                        const double *__restrict__ Y, double *__restrict__ x,
+                                                        const double *__restrict__ scale, const int *__restrict__ mode,
+                                                        const int *__restrict__ gate, double *__restrict__ partials) {
+  __shared__ double lds[4];
+  double beta = 0;
+  if (FUSED) {
+    if (*mode != 0 || (gate && !*gate)) return;
+    beta = *scale;
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double acc[1] = {0};
+  const size_t ngroups = (inc.nslices + 3) / 4;
+  for (size_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const size_t slice = grp * 4 + w;
+    if (slice >= inc.nslices) continue;
+    const int node = inc.perm[slice * 64 + lane];
+    if (node < 0) continue;
+    const size_t i = (size_t)node;
+    double G[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const long long b0 = inc.slice_ptr[slice], b1 = inc.slice_ptr[slice + 1];
+    for (long long k = b0; k < b1; ++k) {
+      const size_t e0 = (size_t)k * 64 + lane;
+      const double we = winc[e0];
+      if (we == 0) continue;
+      const uint32_t code = slot_edge[e0];
+      const size_t e = (size_t)(code >> 1);
+      const double sw = sqrt(we);
+      double Ye[9];
+#pragma unroll
+      for (int c = 0; c < 9; ++c) Ye[c] = Y[9 * e + c];
+      if (code & 1u) {
+        double S[9], YS[9];
+        if (SQ) {
+          const double *sq = Sinc + (size_t)k * 4 * 64 + lane;
+          quat_to_mat(sq[0], sq[64], sq[128], sq[192], S);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 9; ++c) S[c] = Sinc[((size_t)k * 9 + c) * 64 + lane];
+        }
+        mat3_mul(Ye, S, YS);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) G[c] -= sw * YS[c];
+      } else {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) G[c] += sw * Ye[c];
+      }
+    }
+    double Ri[9], Q[9], o[3];
+    load_rot<GQ>(rot, i, Ri);
+    mat3_mul_at(Ri, G, Q);
+    vee_skew2(Q, o);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double t = o[c];
+      if (FUSED) {
+        t = t - beta * x[3 * i + c];
+        acc[0] += t * t;
+      }
+      x[3 * i + c] = t;
+    }
+  }
+  if (FUSED) block_partials_store_nw<1, kNlsBlock / 64>(acc, lds, partials);
+}
+
 int upload(void **dst, const void *src, size_t bytes) {
   MI_HIP(hipMalloc(dst, bytes ? bytes : 8));
   if (bytes) MI_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
@@ -431,6 +625,24 @@ struct mi_so3n {
   // or the model of an older trial point: mi_so3n_model must not swap them in) -- a key of its own, same contents
   // identity.  At most one of the two keys is live: whoever fills grad_next drops the other kind's.
   VecKey armijo;
+  // q->Rq holds the quaternion records of THIS vector (written by the retraction of a fused trial step); cleared when
+  // the assembly converts another point into Rq.  mi_so3n_residual / mi_so3n_jacobian gather quaternions only then.
+  VecKey rq;
+  // ---- nonlinear least-squares view (mi_so3n_residual, mi_so3n_jacobian, mi_so3n_gn_scaling) ----
+  // host copies kept from creation; the device arrays appear when the residual or the Jacobian is first asked for
+  // (TNT / GradientDescent users pay no device memory)
+  std::vector<int32_t> h_ij;        // 2E: (i, j) per edge
+  std::vector<double> h_Se, h_w;    // E * (4 | 9) component-major measurement stream (as sinc_quat says); E weights
+  std::vector<uint32_t> h_slot;     // padded: edge << 1 | (the slot's node is the first node of the edge); padding 0
+  bool w_nonneg = true;
+  int2 *e_ij = nullptr;             // device, E
+  double *Se = nullptr, *swe = nullptr;  // device: E * (4 | 9), E
+  uint32_t *slot_edge = nullptr;    // device, padded (first mi_so3n_jacobian)
+  double *Jrot = nullptr;           // device, 9N: the rotations the bound dF / dF* read (4N used when jac_quat)
+  bool jac_quat = false;
+  mi_op dF, dFt;
+  mi_vec *gn_diag = nullptr;        // 3N: 1 / sqrt(2 degw_i), each three times
+  mi_op *gn_op = nullptr;
 };
 
 namespace {
@@ -450,6 +662,7 @@ void launch_assembly(mi_so3n *q, int form, int grid, const double *R, double *gr
   mi_ctx *ctx = q->ctx;
   const bool gq = q->Rq != nullptr;
   const double *Rq = q->Rq, *Sinc = q->Sinc, *winc = q->winc;
+  if (gq && !have_quat) q->rq.clear();  // (Rq is about to hold the conversion of a point given by address only)
   if (gq && !have_quat)
     hipLaunchKernelGGL(k_so3_quat, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, R, q->Rq);
   DISPATCH_3(form, FORM, SO3_OBJECTIVE, SO3_MODEL, SO3_GRAD, DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(gq, GQ,
@@ -516,6 +729,7 @@ int retract_trial(mi_so3n *q, const mi_vec *R, const mi_vec *xi, mi_vec *Y) {
   hipLaunchKernelGGL(k_so3_retract<true>, dim3(grid_for(q->ctx, q->N, 1)), dim3(kBlock), 0, q->ctx->stream, q->N,
                      (const double *)R->d, (const double *)xi->d, Y->d, q->Rq);
   MI_HIP(hipGetLastError());
+  q->rq.set(Y);
   return MI_OK;
 }
 // The tail of both trial steps: the assembly at the trial point retract_trial produced, in the given form, the gradient
@@ -654,6 +868,24 @@ int mi_so3n_create(mi_ctx *ctx, size_t N, size_t E, const int32_t *ei, const int
         }
       }
   mi_so3n *q = new mi_so3n();
+  // what the least-squares view uploads on first use: end points, weights, the per-edge measurement stream in the form
+  // of Sinc (the same conversion: a second node's slot and the edge stream expand to the same bits), the slot words
+  q->h_ij.resize(2 * E);
+  q->h_w.assign(w, w + E);
+  q->h_Se.resize(E * (size_t)scomp);
+  for (size_t e = 0; e < E; ++e) {
+    q->h_ij[2 * e] = ei[e];
+    q->h_ij[2 * e + 1] = ej[e];
+    if (!(w[e] >= 0)) q->w_nonneg = false;
+    double qv[9];
+    if (all_rot) to_quat(Rt + 9 * e, qv);
+    else std::memcpy(qv, Rt + 9 * e, 9 * sizeof(double));
+    for (int c = 0; c < scomp; ++c) q->h_Se[(size_t)c * E + e] = qv[c];
+  }
+  q->h_slot.assign(padded, 0u);
+  if (E < ((size_t)1 << 31))
+    for (size_t e0 = 0; e0 < padded; ++e0)
+      if (edge[e0] >= 0) q->h_slot[e0] = ((uint32_t)edge[e0] << 1) | (dir[e0] < 0 ? 1u : 0u);
   q->ctx = ctx;
   q->N = N;
   q->E = E;
@@ -700,6 +932,12 @@ int mi_so3n_destroy(mi_so3n *q) {
   mi_vec_destroy(q->grad_next);
   mi_vec_destroy(q->Hh);
   mi_vec_destroy(q->Pg);
+  (void)hipFree(q->e_ij); (void)hipFree(q->Se); (void)hipFree(q->swe); (void)hipFree(q->slot_edge); (void)hipFree(q->Jrot);
+  if (q->gn_op) {
+    q->gn_op->borrowed = false;
+    mi_op_destroy(q->gn_op);
+  }
+  mi_vec_destroy(q->gn_diag);
   delete q;
   return MI_OK;
 }
@@ -881,6 +1119,163 @@ int mi_so3n_armijo_trial(mi_so3n *q, const mi_vec *R, const mi_vec *g, double t,
   out[0] = .25 * buf[0];  // (every edge from both ends)
   out[1] = buf[1];
   q->armijo.set(R_trial);
+  return MI_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the edge streams of the least-squares view, on first use
+int nls_upload(mi_so3n *q, bool with_slots) {
+  MI_REQUIRE(q->w_nonneg, "the least-squares form F_e = sqrt(w_e) (R_j - R_i Rt_e) needs weights >= 0");
+  MI_REQUIRE(!q->ctx->uniform_grid, "the least-squares view of mi_so3n is single-context");
+  if (!q->e_ij) {
+    std::vector<double> sw(q->E);
+    for (size_t e = 0; e < q->E; ++e) sw[e] = std::sqrt(q->h_w[e]);
+    MI_TRY(upload((void **)&q->Se, q->h_Se.data(), q->h_Se.size() * sizeof(double)));
+    MI_TRY(upload((void **)&q->swe, sw.data(), sw.size() * sizeof(double)));
+    MI_TRY(upload((void **)&q->e_ij, q->h_ij.data(), q->h_ij.size() * sizeof(int32_t)));
+  }
+  if (with_slots && !q->slot_edge) {
+    MI_REQUIRE(q->E < ((size_t)1 << 31), "the incidence -> edge words hold edge numbers below 2^31");
+    MI_TRY(upload((void **)&q->slot_edge, q->h_slot.data(), q->h_slot.size() * sizeof(uint32_t)));
+    MI_HIP(hipMalloc((void **)&q->Jrot, q->N * 9 * sizeof(double)));
+  }
+  return MI_OK;
+}
+EdgeView edge_view(const mi_so3n *q) { return EdgeView{q->E, q->e_ij, q->Se, q->swe}; }
+int edge_grid(const mi_so3n *q) {
+  return (int)std::min<size_t>(std::max<size_t>(1, (q->E + kNlsBlock - 1) / kNlsBlock), (size_t)kMaxRows);
+}
+int node_grid(const mi_so3n *q) { return (int)std::min<size_t>(std::max<size_t>(1, (q->nslices + 3) / 4), (size_t)kMaxRows); }
+
+int so3_jac_launch(mi_op *self, const mi_vec *in, mi_vec *out, const double *scale, const int *mode, const int *gate,
+                   double *partials, int *nparts) {
+  mi_so3n *q = (mi_so3n *)self->impl;
+  mi_ctx *ctx = q->ctx;
+  const int grid = edge_grid(q);
+  const bool fused = scale != nullptr;
+  KScope ks(ctx, MI_K_SO3_JAC);
+  DISPATCH_FLAG(fused, FUSED, DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(q->jac_quat, GQ,
+      hipLaunchKernelGGL((k_so3_jac<FUSED, SQ, GQ>), dim3(grid), dim3(kNlsBlock), 0, ctx->stream, edge_view(q),
+                         (const double *)q->Jrot, (const double *)in->d, out->d, scale, mode, gate, partials))));
+  if (nparts) *nparts = grid;
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+int so3_jact_launch(mi_op *self, const mi_vec *in, mi_vec *out, const double *scale, const int *mode, const int *gate,
+                    double *partials, int *nparts) {
+  mi_so3n *q = (mi_so3n *)self->impl;
+  mi_ctx *ctx = q->ctx;
+  const int grid = node_grid(q);
+  const bool fused = scale != nullptr;
+  KScope ks(ctx, MI_K_SO3_JACT);
+  DISPATCH_FLAG(fused, FUSED, DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(q->jac_quat, GQ,
+      hipLaunchKernelGGL((k_so3_jact<FUSED, SQ, GQ>), dim3(grid), dim3(kNlsBlock), 0, ctx->stream, view(q),
+                         (const double *)q->Jrot, (const double *)q->Sinc, (const double *)q->winc,
+                         (const uint32_t *)q->slot_edge, (const double *)in->d, out->d, scale, mode, gate, partials))));
+  if (nparts) *nparts = grid;
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+int so3_jac_apply(mi_op *self, const mi_vec *in, mi_vec *out) {
+  return so3_jac_launch(self, in, out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+int so3_jact_apply(mi_op *self, const mi_vec *in, mi_vec *out) {
+  return so3_jact_launch(self, in, out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+int so3_jac_sub_scaled(mi_op *self, const mi_vec *in, const double *scale, const int *mode, const int *gate, mi_vec *inout,
+                       double *partials, int *nparts) {
+  MI_REQUIRE(scale && mode && partials && nparts, "null argument");
+  return so3_jac_launch(self, in, inout, scale, mode, gate, partials, nparts);
+}
+int so3_jact_sub_scaled(mi_op *self, const mi_vec *in, const double *scale, const int *mode, const int *gate, mi_vec *inout,
+                        double *partials, int *nparts) {
+  MI_REQUIRE(scale && mode && partials && nparts, "null argument");
+  return so3_jact_launch(self, in, inout, scale, mode, gate, partials, nparts);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_so3n_residual(mi_so3n *q, const mi_vec *R, mi_vec *F, double *sqnorm) {
+  SO3_REQUIRE_ARGS(q && R && F);
+  MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
+  MI_REQUIRE(F->ctx == q->ctx && F->n == 9 * q->E, "the residual must hold 9 doubles per edge");
+  mi_ctx *ctx = q->ctx;
+  if (q->E == 0) {
+    if (sqnorm) *sqnorm = 0;
+    return MI_OK;
+  }
+  MI_TRY(nls_upload(q, false));
+  touch(F);
+  // quaternion gathers only at a point whose records the retraction of a fused trial step left in Rq; any other point
+  // is read as it is given (72-byte rows): Rq is not written here, nor anything else a bound Jacobian reads
+  const bool gq = q->Rq && q->rq.is(R);
+  const int grid = edge_grid(q);
+  {
+    KScope ks(ctx, MI_K_SO3_RESIDUAL);
+    DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(gq, GQ,
+        hipLaunchKernelGGL((k_so3_residual<SQ, GQ>), dim3(grid), dim3(kNlsBlock), 0, ctx->stream, edge_view(q),
+                           GQ ? (const double *)q->Rq : (const double *)R->d, F->d, ctx->partials2)));
+  }
+  MI_HIP(hipGetLastError());
+  if (sqnorm) {
+    MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, grid, 1, ctx->scalars + SLOT_MISC));
+    MI_TRY(read_slots_sync(ctx, SLOT_MISC, 1, sqnorm));
+  }
+  return MI_OK;
+}
+
+int mi_so3n_jacobian(mi_so3n *q, const mi_vec *R, mi_op **dF, mi_op **dFt) {
+  SO3_REQUIRE_ARGS(q && R && dF && dFt);
+  MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
+  MI_REQUIRE(q->E > 0, "mi_so3n_jacobian: the problem has no edges (a 3N -> 0 operator)");
+  mi_ctx *ctx = q->ctx;
+  MI_TRY(nls_upload(q, true));
+  // the linearisation's own copy of the rotations: TNLS evaluates F at trial points while LSQR still uses these operators
+  q->jac_quat = q->Rq && q->rq.is(R);
+  if (q->jac_quat) MI_HIP(hipMemcpyAsync(q->Jrot, q->Rq, q->N * 4 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  else MI_HIP(hipMemcpyAsync(q->Jrot, R->d, q->N * 9 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  q->dF = mi_op();
+  q->dF.ctx = ctx;
+  q->dF.n = 3 * q->N;
+  q->dF.n_out = 9 * q->E;
+  q->dF.apply = so3_jac_apply;
+  q->dF.apply_sub_scaled = so3_jac_sub_scaled;
+  q->dF.impl = q;
+  q->dF.borrowed = true;
+  q->dFt = mi_op();
+  q->dFt.ctx = ctx;
+  q->dFt.n = 9 * q->E;
+  q->dFt.n_out = 3 * q->N;
+  q->dFt.apply = so3_jact_apply;
+  q->dFt.apply_sub_scaled = so3_jact_sub_scaled;
+  q->dFt.impl = q;
+  q->dFt.borrowed = true;
+  *dF = &q->dF;
+  *dFt = &q->dFt;
+  return MI_OK;
+}
+
+int mi_so3n_gn_scaling(mi_so3n *q, mi_op **M) {
+  SO3_REQUIRE_ARGS(q && M);
+  MI_REQUIRE(q->w_nonneg, "the Gauss-Newton scaling 1 / sqrt(2 degw) needs weights >= 0");
+  if (!q->gn_op) {
+    std::vector<double> degw(q->N, 0.0), d(3 * q->N);
+    for (size_t e = 0; e < q->E; ++e) {
+      degw[(size_t)q->h_ij[2 * e]] += q->h_w[e];
+      degw[(size_t)q->h_ij[2 * e + 1]] += q->h_w[e];
+    }
+    for (size_t i = 0; i < q->N; ++i) d[3 * i] = d[3 * i + 1] = d[3 * i + 2] = degw[i] > 0 ? 1.0 / std::sqrt(2 * degw[i]) : 1.0;
+    MI_TRY(mi_vec_create(q->ctx, 3 * q->N, &q->gn_diag));
+    MI_TRY(mi_vec_upload(q->gn_diag, d.data(), d.size()));
+    MI_TRY(mi_op_create_diag(q->ctx, q->gn_diag, &q->gn_op));
+    q->gn_op->borrowed = true;
+  }
+  *M = q->gn_op;
   return MI_OK;
 }
 

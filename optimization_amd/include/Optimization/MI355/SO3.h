@@ -5,10 +5,14 @@
 // N row-major 3x3 blocks (9N doubles), Tangent = so(3)^N coordinates (3N doubles), metric =
 // coordinate dot product, retraction R_i exp(hat(xi_i)), preconditioner = 3x3 block-Jacobi built from
 // the Hessian's diagonal blocks.  Kernels: optimization_amd/csrc/so3.hip.
+// The same problem as a nonlinear least-squares one, f = 1/2 |F(R)|^2 with F_e = sqrt(w_e) (R_j - R_i Rt_e) in R^{9E}:
+// residual(), jacobian(), residual_inner_product() and gauss_newton_preconditioner() are the arguments of
+// Riemannian::TNLS (with metric() and retraction() from above); every inner solve then runs in the fused mi_lsqr.
 #pragma once
 
 #include <cstdint>
 
+#include "Optimization/LinearAlgebra/Concepts.h"
 #include "Optimization/MI355/Device.h"
 #include "Optimization/Riemannian/Concepts.h"
 
@@ -21,7 +25,7 @@ class RotationAveraging {
 
   RotationAveraging(const Context &ctx, size_t N, size_t n_edges, const int32_t *ei, const int32_t *ej,
                     const double *Rt, const double *w)
-      : ctx_(ctx), N_(N) {
+      : ctx_(ctx), N_(N), E_(n_edges) {
     check(mi_so3n_create(ctx_.get(), N, n_edges, ei, ej, Rt, w, &prob_));
   }
   RotationAveraging(const RotationAveraging &) = delete;
@@ -113,6 +117,43 @@ class RotationAveraging {
       return Y;
     };
   }
+  // --- Riemannian::TNLS ------------------------------------------------------------------------------------------
+  //   Riemannian::TNLS<Vector, Vector, Vector>(prob.residual(), prob.jacobian(), prob.metric(),
+  //                                            prob.residual_inner_product(), prob.retraction(), R0, precon, params)
+  // F(R): 9 doubles per edge, the caller's edge order (mi_so3n_residual)
+  size_t edges() const { return E_; }
+  template <typename... Args>
+  Riemannian::Mapping<Vector, Vector, Args...> residual() {
+    return [this](const Vector &R, Args &...) {
+      Vector F(ctx_, 9 * E_);
+      check(mi_so3n_residual(prob_, R.handle(), F.handle(), nullptr));
+      return F;
+    };
+  }
+  // (dF_R, dF_R^*) as tagged device operators bound to R (mi_so3n_jacobian): typed without the pack, as TNLS takes it.
+  // The handles are the problem's and are rebound by every call: the pair of the latest linearisation is the valid one.
+  Riemannian::JacobianPairFunction<Vector, Vector, Vector> jacobian() {
+    return [this](const Vector &R) {
+      mi_op *a = nullptr, *at = nullptr;
+      check(mi_so3n_jacobian(prob_, R.handle(), &a, &at));
+      return std::make_pair(Riemannian::Jacobian<Vector, Vector, Vector>(DeviceHessian{a, this}),
+                            Riemannian::JacobianAdjoint<Vector, Vector, Vector>(DeviceHessian{at, this}));
+    };
+  }
+  template <typename... Args>
+  LinearAlgebra::InnerProduct<Vector, double, Args...> residual_inner_product() {
+    return FrobeniusInnerProduct{};
+  }
+  // the right preconditioner pair (M, M') of TNLS, M = M' = diag(1 / sqrt(2 degw_i)): the diagonal blocks of dF* dF are
+  // 2 degw_i I, so this is the block-Jacobi scaling of the Gauss-Newton system (mi_so3n_gn_scaling)
+  template <typename... Args>
+  std::pair<Riemannian::LinearOperator<Vector, Vector, Args...>, Riemannian::LinearOperator<Vector, Vector, Args...>>
+  gauss_newton_preconditioner() {
+    mi_op *m = nullptr;
+    check(mi_so3n_gn_scaling(prob_, &m));
+    return std::make_pair(Riemannian::LinearOperator<Vector, Vector, Args...>(DeviceHessian{m, this}),
+                          Riemannian::LinearOperator<Vector, Vector, Args...>(DeviceHessian{m, this}));
+  }
   // 3x3 block-Jacobi; valid after the first quadratic_model() call (TNT calls QM before precon)
   template <typename... Args>
   Riemannian::LinearOperator<Vector, Vector, Args...> preconditioner() {
@@ -128,7 +169,7 @@ class RotationAveraging {
 
  private:
   Context ctx_;
-  size_t N_;
+  size_t N_, E_;
   mi_so3n *prob_ = nullptr;
   mi_precon *bj_ = nullptr;
 };
