@@ -528,6 +528,31 @@ MI_API int mi_so3n_jacobian(mi_so3n *prob, const mi_vec *R, mi_op **dF, mi_op **
  * three times; 1 for a node of weighted degree 0): the diagonal blocks of dF* dF are exactly 2 degw_i I (|R hat(xi) S|^2 =
  * 2 |xi|^2), so this is the block-Jacobi scaling of the Gauss-Newton system.  Point-independent; owned by the problem. */
 MI_API int mi_so3n_gn_scaling(mi_so3n *prob, mi_op **M);
+/* Global-optimality certificate (as in SE-Sync).  With Y in R^{3N x 3}, Y_i = R_i', and Lap the 3N x 3N connection
+ * Laplacian (diagonal blocks degw_i I, block (i, j) = -w_e Rt_e and (j, i) = -w_e Rt_e' for e = (i -> j)), f(R) = const +
+ * 1/2 tr(Y' Lap Y), and the certificate matrix at R is
+ *   S(R) = Lap - BlockDiag(C_i),  C_i = sym(Q_i),  Q_i = R_i' (L R)_i
+ *   (S v)_i = (degw_i I - C_i) v_i - sum over the incidences of node i, in their fixed slot order, of w_e M' v_nbr
+ * with M = Rt_e' where i is the first node of e and Rt_e where the second.  At every R: tr(Y' S Y) = 0, |S Y|_F =
+ * |skew Q|_F (the stationarity defect, skew Q_i = (Q_i - Q_i') / 2), and f(R') >= f(R) + (3N / 2) min(lambda_min(S), 0)
+ * for every R' in O(3)^N -- so S positive semidefinite at a critical point R certifies the global minimum.
+ * mi_so3n_certificate forms the point-dependent part of S at R in one pass (the walk and the objective partials of
+ * mi_so3n_objective) and returns info[3] = {f(R) with the bits of mi_so3n_objective, |skew Q|_F, sum_i tr C_i}: ONE
+ * read-back (sync).  The handle is owned by the problem (borrowed) and rebound by the next call; it reads a COPY of what
+ * depends on R (the blocks degw_i I - C_i, the panel Y), so later trial steps, model calls and writes to R leave it as it
+ * is.  n_edges = 0 is allowed (S = 0).  Single-context only. */
+typedef struct mi_so3n_cert mi_so3n_cert;
+struct mi_panel_blocks;
+MI_API int mi_so3n_certificate(mi_so3n *prob, const mi_vec *R, mi_so3n_cert **out, double info[3]);
+/* Z = S X on column-major 3N x k panels (ld = 3N, 1 <= k <= 96), no sync, no atomics.  Each column is summed in one fixed
+ * order -- the diagonal block, then the incidences in slot order -- and depends on the same column of X alone: column c of
+ * Z has the same bits whatever k, pass or column-block split produced it.  Z must not overlap X.  The _blocks form takes
+ * the input as 1 to 3 column blocks (mi_panel_blocks, section (8)): the same columns, the same bits. */
+MI_API int mi_so3n_cert_apply(mi_so3n_cert *cert, int k, const mi_vec *X, mi_vec *Z);
+MI_API int mi_so3n_cert_apply_blocks(mi_so3n_cert *cert, const struct mi_panel_blocks *X, mi_vec *Z);
+/* The 3N x 3 column-major panel Y (Y(3i + r, c) = R_i[c][r]) at the certificate's point: S Y = 0 at a critical point, so
+ * these are the three eigenvectors at (or near) 0 -- the start block of an eigensolver deflates them.  Borrowed. */
+MI_API int mi_so3n_cert_null_panel(mi_so3n_cert *cert, mi_vec **Y);
 
 /* ---------------------------------------------------------------------------------------------
  * (8) LOBPCG building blocks (LinearAlgebra/LOBPCG.h:131-337).  Panels are column-major m x k

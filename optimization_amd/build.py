@@ -143,7 +143,9 @@ def build_harness(force=False):
       tests/cpp/libharness_lsqr_observer.so  LSQR with a user function: C ABI and template layer
       tests/cpp/libharness_gd_so3n.so GradientDescent on MI355::RotationAveraging (fused Armijo trial and its controls)
       tests/cpp/libharness_tnls_so3n.so TNLS on MI355::RotationAveraging as a least-squares problem: host restatement,
-                                      tagged device accessors, the same operators behind plain lambdas"""
+                                      tagged device accessors, the same operators behind plain lambdas
+      tests/cpp/libharness_certify_so3n.so MI355::RotationAveraging::certify: the certificate operator through LOBPCG,
+                                      tagged and behind a plain lambda, after an optional TNT run"""
     tdir = os.path.join(ROOT, "tests", "cpp")
     inc = ["-I", os.path.join(HERE, "include"), "-I", os.path.join(ROOT, "oracle")]
     common = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-type-limits"]
@@ -187,7 +189,7 @@ def build_harness(force=False):
     out.append(ob_so)
     # tests/cpp/harness_args.cpp, harness_lsqr_observer.cpp, harness_gd_so3n.cpp, harness_tnls_so3n.cpp: g++, and clang's front end on the same
     # translation units (the pack-carrying instantiations of the template layer must pass both)
-    for name in ("harness_args", "harness_lsqr_observer", "harness_gd_so3n", "harness_tnls_so3n"):
+    for name in ("harness_args", "harness_lsqr_observer", "harness_gd_so3n", "harness_tnls_so3n", "harness_certify_so3n"):
         src = os.path.join(tdir, name + ".cpp")
         so = os.path.join(tdir, "lib" + name + ".so")
         if force or _newer(src, so, hdrs + [LIB]):

@@ -204,6 +204,10 @@ def load():
         "mi_so3n_residual": [vp, vp, vp, c_double_p],
         "mi_so3n_jacobian": [vp, vp, C.POINTER(vp), C.POINTER(vp)],
         "mi_so3n_gn_scaling": [vp, C.POINTER(vp)],
+        "mi_so3n_certificate": [vp, vp, C.POINTER(vp), c_double_p],
+        "mi_so3n_cert_apply": [vp, C.c_int, vp, vp],
+        "mi_so3n_cert_apply_blocks": [vp, C.POINTER(PanelBlocks), vp],
+        "mi_so3n_cert_null_panel": [vp, C.POINTER(vp)],
         "mi_stpcg_collect": [vp, C.POINTER(StpcgResult)],
         "mi_lobpcg_gram": [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, c_double_p],
         "mi_lobpcg_update": [vp, C.c_size_t, C.c_int, C.c_int, vp, c_double_p, C.c_int, vp],
@@ -1181,6 +1185,14 @@ class So3N:
         M.n_in = M.n_out = 3 * self.N
         return M
 
+    def certificate(self, R):
+        """mi_so3n_certificate: (So3NCertificate bound to a copy of what depends on R, dict(f, stationarity, trace_C));
+        problem-owned, rebound by the next call"""
+        h = vp()
+        out = np.zeros(3)
+        check(self.L.mi_so3n_certificate(self.h, R.h, C.byref(h), _dp(out)))
+        return So3NCertificate(self, h), dict(f=out[0], stationarity=out[1], trace_C=out[2])
+
     def armijo_trial(self, R, g, t, h=None, R_trial=None):
         """mi_so3n_armijo_trial: (h = -t g Vec, R_trial Vec, dict(f, grad_sqnorm))"""
         h = h if h is not None else Vec(self.ctx, 3 * self.N)
@@ -1195,6 +1207,35 @@ class So3N:
                 self.L.mi_so3n_destroy(self.h)
         except Exception:  # noqa
             pass
+
+
+class So3NCertificate:
+    """The certificate matrix S(R) of a So3N problem (mi_so3n_cert_*): borrowed from the problem, which it keeps alive."""
+
+    def __init__(self, prob, h):
+        self.prob, self.ctx, self.L, self.h, self.m = prob, prob.ctx, prob.L, h, 3 * prob.N
+
+    def apply(self, k, X, Z=None):
+        """mi_so3n_cert_apply: Z = S X on column-major 3N x k panels"""
+        Z = Z if Z is not None else Vec(self.ctx, self.m * k)
+        check(self.L.mi_so3n_cert_apply(self.h, k, X.h, Z.h))
+        return Z
+
+    def apply_blocks(self, blocks, Z=None):
+        """mi_so3n_cert_apply_blocks: S [block 0 | block 1 | ...] for column blocks [(panel or view, columns), ...]"""
+        k = sum(c for _, c in blocks)
+        Z = Z if Z is not None else Vec(self.ctx, self.m * k)
+        pb = PanelBlocks.of(blocks)
+        check(self.L.mi_so3n_cert_apply_blocks(self.h, C.byref(pb), Z.h))
+        return Z
+
+    def null_panel(self):
+        """mi_so3n_cert_null_panel: the 3N x 3 column-major panel Y, Y_i = R_i', as a borrowed Vec"""
+        h = vp()
+        check(self.L.mi_so3n_cert_null_panel(self.h, C.byref(h)))
+        v = Vec(self.ctx, 0, handle=h)
+        v.keep = self
+        return v
 
 
 class StiefelRQ:

@@ -591,6 +591,201 @@ __global__ __launch_bounds__(kNlsBlock) void k_so3_jact(IncView inc, const doubl
   if (FUSED) block_partials_store_nw<1, kNlsBlock / 64>(acc, lds, partials);
 }
 
+// ---- global-optimality certificate -----------------------------------------------------------------------
+// With Y in R^{3N x 3}, Y_i = R_i', and the 3N x 3N connection Laplacian (diagonal blocks degw_i I, block (i, j) = -w_e Rt_e
+// and (j, i) = -w_e Rt_e' for e = (i -> j)), f(R) = const + 1/2 tr(Y' Lap Y), and the certificate matrix at R is
+//     S(R) = Lap - BlockDiag(C_i),  C_i = sym(Q_i)
+//     (S v)_i = (degw_i I - C_i) v_i - sum_{inc of i, slot order} w S_inc' v_nbr
+// (S_inc: what Sinc holds for the slot).  tr(Y' S Y) = 0 at every R, |S Y|_F = |skew Q|_F, and for every R' in O(3)^N
+// f(R') >= f(R) + (3N / 2) min(lambda_min(S), 0): S positive semidefinite at a critical point certifies the global minimum.
+// The off-diagonal blocks are the static streams Sinc / winc / nbr; only the N diagonal blocks depend on the point.
+//
+// k_so3_cert_diag: one lane per node, the walk, the gathers and the objective partial of k_so3_model<false, ...> (grid,
+// workgroup shape and accumulation order: the bits of mi_so3n_objective), leaving per node
+//   the six distinct entries (00, 01, 02, 11, 12, 22) of E_i = degw_i I - C_i in slice order (entry c of (slice, lane) at
+//   (slice * 6 + c) * 64 + lane; padding lanes: 0), and row c of R_i as rows 3i .. 3i+2 of column c of the column-major
+//   3N x 3 panel Yp (Y(3i + r, c) = R_i[c][r]);
+// and per workgroup three partial rows: the objective sum, |Q_i - Q_i'|_F^2 and tr C_i (components of kModelComps rows
+// groups each, laid out as the objective's).  A body of its own: see k_so3_grad on sharing one with k_so3_model.
+constexpr int kCertComps = 8;  // == kModelComps (below): partial components per quantity
+template <bool SQ, bool GQ>
+__global__ __launch_bounds__(256) void k_so3_cert_diag(IncView inc, const double *__restrict__ R, const double *__restrict__ Rq,
+                                                       const double *__restrict__ Sinc, const double *__restrict__ winc,
+                                                       double *__restrict__ Esl, double *__restrict__ Yp,
+                                                       double *__restrict__ fpartials) {
+  __shared__ double flds[12];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double facc = 0, gacc = 0, tacc = 0;
+  const size_t ngroups = (inc.nslices + 3) / 4, ld = 3 * inc.N;
+  for (size_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const size_t slice = grp * 4 + w;
+    if (slice >= inc.nslices) continue;
+    const int node = inc.perm[slice * 64 + lane];
+    const bool live = node >= 0;
+    const size_t i = live ? (size_t)node : 0;
+    double Ri[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) Ri[c] = live ? R[9 * i + c] : (c % 4 == 0 ? 1.0 : 0.0);
+    double EG[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double degw = 0;
+    const long long b0 = inc.slice_ptr[slice], b1 = inc.slice_ptr[slice + 1];
+    for (long long k = b0; k < b1; ++k) {
+      const size_t e0 = (size_t)k * 64 + lane;
+      const double we = winc[e0];
+      if (live && we != 0) {
+        const size_t j = (size_t)inc.nbr[e0];
+        double S[9], Rj[9];
+        if (GQ) {
+          const double2 qa = *reinterpret_cast<const double2 *>(Rq + 4 * j), qb = *reinterpret_cast<const double2 *>(Rq + 4 * j + 2);
+          quat_to_mat(qa.x, qa.y, qb.x, qb.y, Rj);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 9; ++c) Rj[c] = R[9 * j + c];
+        }
+        if (SQ) {
+          const double *sq = Sinc + (size_t)k * 4 * 64 + lane;
+          quat_to_mat(sq[0], sq[64], sq[128], sq[192], S);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 9; ++c) S[c] = Sinc[((size_t)k * 9 + c) * 64 + lane];
+        }
+        double RjS[9];
+        mat3_mul(Rj, S, RjS);
+        double q = 0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+          const double d = Ri[c] - RjS[c];
+          EG[c] += we * d;
+          q += d * d;
+        }
+        facc += we * q;
+        degw += we;
+      }
+    }
+    double *Es = Esl + slice * 6 * 64 + lane;
+    if (!live) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) Es[c * 64] = 0.0;
+      continue;
+    }
+    double Q[9];
+    mat3_mul_at(Ri, EG, Q);
+    const double c01 = .5 * (Q[1] + Q[3]), c02 = .5 * (Q[2] + Q[6]), c12 = .5 * (Q[5] + Q[7]);
+    Es[0] = degw - Q[0]; Es[64] = -c01; Es[128] = -c02;
+    Es[192] = degw - Q[4]; Es[256] = -c12; Es[320] = degw - Q[8];
+    const double s0 = Q[7] - Q[5], s1 = Q[2] - Q[6], s2 = Q[3] - Q[1];
+    gacc += 2 * (s0 * s0 + s1 * s1 + s2 * s2);
+    tacc += Q[0] + Q[4] + Q[8];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) Yp[(size_t)c * ld + 3 * i + r] = Ri[3 * c + r];
+  }
+  facc = wave_reduce_sum(facc);
+  gacc = wave_reduce_sum(gacc);
+  tacc = wave_reduce_sum(tacc);
+  if (lane == 0) { flds[w] = facc; flds[4 + w] = gacc; flds[8 + w] = tacc; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    // (the rows of each quantity laid out, and its unused rows zeroed, as k_so3_model does for the objective)
+    double *part = fpartials + (size_t)threadIdx.x * kCertComps * kMaxRows;
+    const double *l = flds + 4 * threadIdx.x;
+    part[(size_t)(blockIdx.x / kMaxRows) * kMaxRows + blockIdx.x % kMaxRows] = (l[0] + l[1]) + (l[2] + l[3]);
+    const size_t total = (size_t)((gridDim.x + kMaxRows - 1) / kMaxRows) * kMaxRows, z = (size_t)gridDim.x + blockIdx.x;
+    if (z < total) part[z] = 0.0;
+  }
+}
+
+// The input panel of the certificate product as up to three column blocks (mi_panel_blocks): column c is column c of
+// block 0 for c < n0, column c - n0 of block 1 for c < n01, else column c - n01 of block 2 (one panel: n0 = n01 = k)
+struct CertCols {
+  const double *b[3];
+  int n0, n01;
+};
+// (the expansion with contraction off: an incidence and its mirror image at the other node hold conjugate quaternions, and
+// rounded products make their two expansions exact transposes of each other)
+__device__ __forceinline__ void quat_to_mat_nc(double w, double x, double y, double z, double *S) {
+#pragma clang fp contract(off)
+  const double xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+  S[0] = 1 - 2 * (yy + zz); S[1] = 2 * (xy - wz);     S[2] = 2 * (xz + wy);
+  S[3] = 2 * (xy + wz);     S[4] = 1 - 2 * (xx + zz); S[5] = 2 * (yz - wx);
+  S[6] = 2 * (xz - wy);     S[7] = 2 * (yz + wx);     S[8] = 1 - 2 * (xx + yy);
+}
+// Z = S X on column-major 3N x k panels (ld = 3N), one lane per node, 4 slices per workgroup; blockIdx.y: the pass (KC
+// columns each, the last one possibly fewer), all passes in one launch as in k_spmm_colmajor_win.  An incidence's weight,
+// neighbour and measurement are loaded -- and the measurement expanded -- ONCE and applied to the pass's columns: the
+// matrix stream (8 + 4 + 32 (72) bytes per incidence) is amortised over KC columns, the neighbour's three rows are gathered
+// per column.  Every column is summed in one fixed order with contraction off -- the diagonal block's row products left
+// to right, then the incidences in slot order, each as z_r - w (S_0r y_0 + S_1r y_1 + S_2r y_2) -- so column c of Z depends
+// on column c of X alone and has the same bits whatever k, KC, pass or column-block split it came from.  Weight-0 slots
+// (padding, or an edge of weight 0) and padding lanes do nothing.  Z must not overlap X.
+// Algorithmic bytes per application, P = ceil(k / KC) passes: P (nnzb (12 + 32 (72)) + 52 N) + 48 k N  [+ 24 k nnzb gathered]
+template <int KC, bool SQ>
+__global__ __launch_bounds__(256) void k_so3_cert_panel(IncView inc, const double *__restrict__ Sinc,
+                                                        const double *__restrict__ winc, const double *__restrict__ Esl,
+                                                        CertCols X, int k, double *__restrict__ Z) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const size_t ld = 3 * inc.N;
+  const int c0 = (int)blockIdx.y * KC, nc = k - c0 < KC ? k - c0 : KC;
+  const double *xc[KC];
+#pragma unroll
+  for (int c = 0; c < KC; ++c) {
+    const int cc = c0 + (c < nc ? c : 0);
+    xc[c] = cc < X.n0 ? X.b[0] + (size_t)cc * ld : cc < X.n01 ? X.b[1] + (size_t)(cc - X.n0) * ld : X.b[2] + (size_t)(cc - X.n01) * ld;
+  }
+  const size_t ngroups = (inc.nslices + 3) / 4;
+  for (size_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const size_t slice = grp * 4 + w;
+    if (slice >= inc.nslices) continue;
+    const int node = inc.perm[slice * 64 + lane];
+    if (node < 0) continue;
+    const size_t i = (size_t)node;
+    const double *Es = Esl + slice * 6 * 64 + lane;
+    const double e00 = Es[0], e01 = Es[64], e02 = Es[128], e11 = Es[192], e12 = Es[256], e22 = Es[320];
+    double z[KC][3];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      z[c][0] = z[c][1] = z[c][2] = 0;
+      if (c < nc) {
+        const double x0 = xc[c][3 * i], x1 = xc[c][3 * i + 1], x2 = xc[c][3 * i + 2];
+        z[c][0] = e00 * x0 + e01 * x1 + e02 * x2;
+        z[c][1] = e01 * x0 + e11 * x1 + e12 * x2;
+        z[c][2] = e02 * x0 + e12 * x1 + e22 * x2;
+      }
+    }
+    const long long b0 = inc.slice_ptr[slice], b1 = inc.slice_ptr[slice + 1];
+    for (long long s = b0; s < b1; ++s) {
+      const size_t e0 = (size_t)s * 64 + lane;
+      const double we = winc[e0];
+      if (we == 0) continue;
+      const size_t j = (size_t)inc.nbr[e0];
+      double S[9];
+      if (SQ) {
+        const double *sq = Sinc + (size_t)s * 4 * 64 + lane;
+        quat_to_mat_nc(sq[0], sq[64], sq[128], sq[192], S);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) S[c] = Sinc[((size_t)s * 9 + c) * 64 + lane];
+      }
+#pragma unroll
+      for (int c = 0; c < KC; ++c)
+        if (c < nc) {
+          const double y0 = xc[c][3 * j], y1 = xc[c][3 * j + 1], y2 = xc[c][3 * j + 2];
+          z[c][0] = z[c][0] - we * (S[0] * y0 + S[3] * y1 + S[6] * y2);
+          z[c][1] = z[c][1] - we * (S[1] * y0 + S[4] * y1 + S[7] * y2);
+          z[c][2] = z[c][2] - we * (S[2] * y0 + S[5] * y1 + S[8] * y2);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < KC; ++c)
+      if (c < nc) {
+        double *zc = Z + (size_t)(c0 + c) * ld + 3 * i;
+        zc[0] = z[c][0]; zc[1] = z[c][1]; zc[2] = z[c][2];
+      }
+  }
+}
+
 int upload(void **dst, const void *src, size_t bytes) {
   MI_HIP(hipMalloc(dst, bytes ? bytes : 8));
   if (bytes) MI_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
@@ -598,6 +793,14 @@ int upload(void **dst, const void *src, size_t bytes) {
 }
 
 }  // namespace
+
+// The certificate matrix S(R) of mi_so3n_certificate: the problem's static incidence streams plus a copy of what depends
+// on the point (the diagonal blocks E_i = degw_i I - C_i, the panel Y), written by k_so3_cert_diag and by nothing else
+struct mi_so3n_cert {
+  mi_so3n *q = nullptr;
+  double *Esl = nullptr;  // nslices * 6 * 64: the six distinct entries of E_i in slice order
+  mi_vec *Y = nullptr;    // 9N: the column-major 3N x 3 panel Y, Y_i = R_i'
+};
 
 struct mi_so3n {
   mi_ctx *ctx = nullptr;
@@ -643,6 +846,7 @@ struct mi_so3n {
   mi_op dF, dFt;
   mi_vec *gn_diag = nullptr;        // 3N: 1 / sqrt(2 degw_i), each three times
   mi_op *gn_op = nullptr;
+  mi_so3n_cert *cert = nullptr;     // mi_so3n_certificate: owned here, rebound by every call
 };
 
 namespace {
@@ -650,6 +854,7 @@ namespace {
 // workgroups of the model assembly: one per group of 4 slices while their objective partials fit 8 components of
 // kMaxRows rows (N <= 2.1e6 rotations), a grid-stride walk beyond
 constexpr int kModelComps = 8;
+static_assert(kCertComps == kModelComps, "k_so3_cert_diag lays its partial rows out as k_so3_model does");
 int model_grid(const mi_so3n *q) { return (int)std::min<size_t>((q->nslices + 3) / 4, (size_t)kModelComps * kMaxRows); }
 IncView view(const mi_so3n *q) {
   return IncView{q->N, q->nslices, q->slice_ptr, q->perm, q->nbr};
@@ -938,6 +1143,11 @@ int mi_so3n_destroy(mi_so3n *q) {
     mi_op_destroy(q->gn_op);
   }
   mi_vec_destroy(q->gn_diag);
+  if (q->cert) {
+    (void)hipFree(q->cert->Esl);
+    mi_vec_destroy(q->cert->Y);
+    delete q->cert;
+  }
   delete q;
   return MI_OK;
 }
@@ -1276,6 +1486,124 @@ int mi_so3n_gn_scaling(mi_so3n *q, mi_op **M) {
     q->gn_op->borrowed = true;
   }
   *M = q->gn_op;
+  return MI_OK;
+}
+
+// ---- global-optimality certificate (kernels: k_so3_cert_diag, k_so3_cert_panel) ----
+}  // extern "C"
+
+namespace {
+
+// quantity `which` (0 objective sum, 1 |Q - Q'|^2, 2 tr C) of k_so3_cert_diag's partial rows -> one sum in *slot, reduced
+// as model_objective_to_slot reduces the objective (which == 0: that very function)
+int cert_rows_to_slot(mi_so3n *q, int grid, int which, double *slot) {
+  mi_ctx *ctx = q->ctx;
+  if (which == 0) return model_objective_to_slot(q, grid, slot);
+  const double *rows = ctx->partials2 + (size_t)which * kCertComps * kMaxRows;
+  const int comps = (grid + kMaxRows - 1) / kMaxRows;
+  if (comps == 1) return reduce_rows_allreduce(ctx, rows, grid, 1, slot);
+  double *tmp = ctx->scalars + SLOT_RAW + which * kCertComps;
+  MI_TRY(reduce_rows_allreduce(ctx, rows, kMaxRows, comps, tmp));
+  hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(1), 0, ctx->stream, (const double *)tmp, comps, slot);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+int cert_launch(const mi_so3n_cert *c, const CertCols &X, int k, double *Z) {
+  const mi_so3n *q = c->q;
+  mi_ctx *ctx = q->ctx;
+  const int KCsel = k == 1 ? 1 : k <= 4 ? 4 : 8;
+  const dim3 grid((unsigned)std::min<size_t>(std::max<size_t>(1, (q->nslices + 3) / 4), 4096), (unsigned)((k + KCsel - 1) / KCsel));
+#define CERT_PANEL(KCV)                                                                                                     \
+  DISPATCH_FLAG(q->sinc_quat, SQ,                                                                                           \
+                hipLaunchKernelGGL((k_so3_cert_panel<KCV, SQ>), grid, dim3(256), 0, ctx->stream, view(q),                   \
+                                   (const double *)q->Sinc, (const double *)q->winc, (const double *)c->Esl, X, k, Z))
+  if (KCsel == 1) { CERT_PANEL(1); }
+  else if (KCsel == 4) { CERT_PANEL(4); }
+  else { CERT_PANEL(8); }
+#undef CERT_PANEL
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+constexpr int kCertMaxK = 96;  // the widest panel of the LOBPCG building blocks (lobpcg.hip: kGramMaxK)
+// Z (3N x k) against an input block of `cols` columns: both in the certificate's context, large enough, not overlapping
+int cert_check_io(const mi_so3n_cert *c, const mi_vec *X, int cols, const mi_vec *Z, int k) {
+  const size_t m = 3 * c->q->N;
+  MI_REQUIRE(X->ctx == c->q->ctx && Z->ctx == c->q->ctx, "panel belongs to another context");
+  MI_REQUIRE(X->n >= m * (size_t)cols, "X holds %zu doubles, needs 3N * k = %zu * %d", X->n, m, cols);
+  MI_REQUIRE(Z->n >= m * (size_t)k, "Z holds %zu doubles, needs 3N * k = %zu * %d", Z->n, m, k);
+  MI_REQUIRE(Z->d + m * (size_t)k <= X->d || X->d + m * (size_t)cols <= Z->d, "input and output panels must not overlap");
+  return MI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_so3n_certificate(mi_so3n *q, const mi_vec *R, mi_so3n_cert **out, double info[3]) {
+  SO3_REQUIRE_ARGS(q && R && out && info);
+  MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
+  mi_ctx *ctx = q->ctx;
+  MI_REQUIRE(!ctx->uniform_grid, "the certificate of mi_so3n is single-context");
+  if (!q->cert) {
+    mi_so3n_cert *c = new mi_so3n_cert();
+    c->q = q;
+    q->cert = c;
+    MI_HIP(hipMalloc((void **)&c->Esl, q->nslices * 6 * 64 * sizeof(double)));
+    MI_TRY(mi_vec_create(ctx, 9 * q->N, &c->Y));
+  }
+  mi_so3n_cert *c = q->cert;
+  touch(c->Y);
+  // the neighbours gathered as mi_so3n_objective gathers them (quaternion records when the problem keeps them: those the
+  // retraction of a fused trial step left for this very point, else converted here first)
+  const bool gq = q->Rq != nullptr, have_quat = gq && q->rq.is(R);
+  if (gq && !have_quat) {
+    q->rq.clear();
+    hipLaunchKernelGGL(k_so3_quat, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, (const double *)R->d, q->Rq);
+  }
+  const int grid = model_grid(q);
+  DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(gq, GQ,
+      hipLaunchKernelGGL((k_so3_cert_diag<SQ, GQ>), dim3(grid), dim3(256), 0, ctx->stream, view(q), (const double *)R->d,
+                         (const double *)q->Rq, (const double *)q->Sinc, (const double *)q->winc, c->Esl, c->Y->d,
+                         ctx->partials2)));
+  MI_HIP(hipGetLastError());
+  for (int which = 0; which < 3; ++which) MI_TRY(cert_rows_to_slot(q, grid, which, ctx->scalars + SLOT_MISC + which));
+  double buf[3];
+  MI_TRY(read_slots_sync(ctx, SLOT_MISC, 3, buf));  // the one read-back
+  info[0] = .25 * buf[0];  // (every edge from both ends)
+  info[1] = .5 * std::sqrt(buf[1]);  // |skew Q|_F with skew Q_i = (Q_i - Q_i') / 2: the sum holds |Q_i - Q_i'|_F^2
+  info[2] = buf[2];
+  *out = c;
+  return MI_OK;
+}
+
+int mi_so3n_cert_apply(mi_so3n_cert *c, int k, const mi_vec *X, mi_vec *Z) {
+  SO3_REQUIRE_ARGS(c && X && Z);
+  MI_REQUIRE(k >= 1 && k <= kCertMaxK, "panel width must be in [1,%d]", kCertMaxK);
+  MI_TRY(cert_check_io(c, X, k, Z, k));
+  touch(Z);
+  return cert_launch(c, CertCols{{X->d, X->d, X->d}, k, k}, k, Z->d);
+}
+
+int mi_so3n_cert_apply_blocks(mi_so3n_cert *c, const mi_panel_blocks *X, mi_vec *Z) {
+  SO3_REQUIRE_ARGS(c && X && Z);
+  MI_REQUIRE(X->nblocks >= 1 && X->nblocks <= 3, "a panel has 1 to 3 column blocks");
+  int k = 0;
+  for (int b = 0; b < X->nblocks; ++b) {
+    MI_REQUIRE(X->block[b] && X->cols[b] >= 1, "column block %d is empty", b);
+    k += X->cols[b];
+  }
+  MI_REQUIRE(k <= kCertMaxK, "panel width must be in [1,%d]", kCertMaxK);
+  for (int b = 0; b < X->nblocks; ++b) MI_TRY(cert_check_io(c, X->block[b], X->cols[b], Z, k));
+  const double *b0 = X->block[0]->d, *b1 = X->nblocks > 1 ? X->block[1]->d : b0, *b2 = X->nblocks > 2 ? X->block[2]->d : b1;
+  const int n0 = X->nblocks > 1 ? X->cols[0] : k, n01 = X->nblocks > 2 ? n0 + X->cols[1] : k;
+  touch(Z);
+  return cert_launch(c, CertCols{{b0, b1, b2}, n0, n01}, k, Z->d);
+}
+
+int mi_so3n_cert_null_panel(mi_so3n_cert *c, mi_vec **Y) {
+  SO3_REQUIRE_ARGS(c && Y);
+  *Y = c->Y;
   return MI_OK;
 }
 

@@ -8,16 +8,70 @@
 // The same problem as a nonlinear least-squares one, f = 1/2 |F(R)|^2 with F_e = sqrt(w_e) (R_j - R_i Rt_e) in R^{9E}:
 // residual(), jacobian(), residual_inner_product() and gauss_newton_preconditioner() are the arguments of
 // Riemannian::TNLS (with metric() and retraction() from above); every inner solve then runs in the fused mi_lsqr.
+// Global optimality: certificate_operator(R) is the certificate matrix S(R) of mi_so3n_certificate as a
+// SymmetricLinearOperator on device panels, certify(R) its smallest eigenvalue through LinearAlgebra::LOBPCG and the
+// verdict that follows from it.
 #pragma once
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <optional>
 
 #include "Optimization/LinearAlgebra/Concepts.h"
+#include "Optimization/LinearAlgebra/LOBPCG.h"
 #include "Optimization/MI355/Device.h"
+#include "Optimization/MI355/Matrix.h"
 #include "Optimization/Riemannian/Concepts.h"
 
 namespace Optimization {
 namespace MI355 {
+
+// The certificate matrix S(R) (mi355opt.h: mi_so3n_certificate) as a callable on column-major 3N x k device panels --
+// tagged: what RotationAveraging::certificate_operator returns inside a SymmetricLinearOperator<DeviceMatrix>, to be found
+// again with std::function::target.  The handle is the problem's and is rebound by the next certificate_operator() /
+// certify() call: the operator of the latest call is the valid one.
+struct CertificateOperator {
+  mi_so3n_cert *cert = nullptr;
+  const void *owner = nullptr;
+  size_t N = 0;
+  double f = 0;             // f(R), the bits of mi_so3n_objective
+  double stationarity = 0;  // |skew Q|_F = |S Y|_F
+  double trace_C = 0;       // sum_i tr C_i
+  DeviceMatrix operator()(const DeviceMatrix &X) const {
+    DeviceMatrix Z(X.context(), X.rows(), X.cols());
+    check(mi_so3n_cert_apply(cert, (int)X.cols(), X.handle(), Z.handle()));
+    return Z;
+  }
+  // S [block 0 | block 1 | ...] of a panel held as column blocks: nothing is copied together
+  DeviceMatrix operator()(const PanelBlocks &X) const {
+    DeviceMatrix Z(X.context(), X.rows(), X.cols());
+    const mi_panel_blocks b = X.raw();
+    check(mi_so3n_cert_apply_blocks(cert, &b, Z.handle()));
+    return Z;
+  }
+};
+
+struct CertifyParams {
+  size_t nx = 6;                 // block size of the eigensolver (at most N): wider than the eigenvalue cluster at 0
+  double tau = 1e-8;             // LOBPCG's relative residual tolerance
+  size_t max_iterations = 1000;
+  double eta = -1;               // certified <=> converged and lambda_min_safe >= -eta; negative: the default (see certify)
+  std::optional<LinearAlgebra::SymmetricLinearOperator<DeviceMatrix>> preconditioner;  // LOBPCG's T
+};
+struct CertifyResult {
+  double lambda_min = 0;       // theta_0, the smallest Ritz value
+  double lambda_min_safe = 0;  // theta_0 - |r_0| / |x_0|: no eigenvalue-free interval [theta_0 - |r|/|x|, theta_0 + |r|/|x|]
+  DeviceMatrix eigenvector;    // 3N x 1 (empty when no solve was needed)
+  double f = 0;                // f(R)
+  double lower_bound = 0;      // f + 1.5 N min(lambda_min_safe, 0) <= min over O(3)^N of f, PROVIDED theta_0 tracks the smallest
+                               // eigenvalue of S (LOBPCG converges to it from a generic start block; it is not proved to)
+  double stationarity = 0;     // |skew Q|_F
+  double norm_estimate = 0;    // |S| from one Gaussian probe
+  double eta = 0;              // the threshold used
+  size_t iterations = 0;
+  bool converged = false, certified = false;
+};
 
 class RotationAveraging {
  public:
@@ -153,6 +207,65 @@ class RotationAveraging {
     check(mi_so3n_gn_scaling(prob_, &m));
     return std::make_pair(Riemannian::LinearOperator<Vector, Vector, Args...>(DeviceHessian{m, this}),
                           Riemannian::LinearOperator<Vector, Vector, Args...>(DeviceHessian{m, this}));
+  }
+  // --- global optimality ------------------------------------------------------------------------------------------
+  // S(R) as LOBPCG's operator A (a CertificateOperator inside: target<CertificateOperator>() has f, the stationarity
+  // defect and the panel Y).  Bound to a copy of what depends on R: trial steps, model calls and writes to R leave it alone.
+  LinearAlgebra::SymmetricLinearOperator<DeviceMatrix> certificate_operator(const Vector &R) {
+    CertificateOperator op;
+    op.owner = this;
+    op.N = N_;
+    double info[3];
+    check(mi_so3n_certificate(prob_, R.handle(), &op.cert, info));
+    op.f = info[0];
+    op.stationarity = info[1];
+    op.trace_C = info[2];
+    return op;
+  }
+  // Is the critical point R the global minimiser?  lambda_min(S(R)) by LOBPCG (nev = 1) from a Gaussian start block, drawn
+  // like gaussian_probe with the default-seeded engine.  The block is wider than the three eigenvalues S always has at (or
+  // near) 0 -- S Y = 0 at a critical point -- so the cluster does not slow the lowest pair down.  Y itself is NOT put into
+  // the start block: its columns are eigenvectors with a residual of rounding size (exactly 0 for the axis column of the
+  // winding), which the solver's equilibrated Rayleigh-Ritz step cannot take ("B is not positive definite"), and with
+  // nev = 1 the solver would stop on one of them after one iteration, before a negative eigenvalue of a large graph has
+  // entered the search space.  mi_so3n_cert_null_panel hands Y to clients that deflate it themselves.
+  // certified <=> converged and lambda_min_safe >= -eta, by default eta = 2 tau |S|est + stationarity -- what the
+  // eigenvalue cannot resolve: the solver's own residual test, and the distance of Y from an exact null vector.
+  CertifyResult certify(const Vector &R, const CertifyParams &params = CertifyParams()) {
+    const auto A = certificate_operator(R);
+    return certify_with(A, *A.target<CertificateOperator>(), params);
+  }
+  // the same with the operator handed to LOBPCG as given (e.g. `info` wrapped in a plain lambda)
+  CertifyResult certify_with(const LinearAlgebra::SymmetricLinearOperator<DeviceMatrix> &A, const CertificateOperator &info,
+                             const CertifyParams &params) {
+    using Op = LinearAlgebra::SymmetricLinearOperator<DeviceMatrix>;
+    CertifyResult out;
+    out.f = info.f;
+    out.stationarity = info.stationarity;
+    if (E_ == 0) {  // S = 0
+      out.lower_bound = out.f;
+      out.converged = out.certified = true;
+      return out;
+    }
+    const size_t m = 3 * N_, nx = std::max<size_t>(1, std::min(params.nx, N_));
+    const DeviceMatrix X0 = gaussian_probe(DeviceMatrix(ctx_, 1, 1), m, nx);
+    out.norm_estimate = A(X0).norm() / X0.norm();  // (the estimate LOBPCG forms from its own probe: the same draw)
+    out.eta = params.eta >= 0 ? params.eta : 2 * params.tau * out.norm_estimate + out.stationarity;
+    size_t iters = 0, nc = 0;
+    const size_t nev = 1;
+    auto tx = LinearAlgebra::LOBPCG<HostVectorD, DeviceMatrix, double>(A, std::optional<Op>(), params.preconditioner, X0, nev,
+                                                                       params.max_iterations, iters, nc, params.tau);
+    out.lambda_min = tx.first(0);
+    const DeviceMatrix x0col = tx.second.leftCols(1);
+    out.eigenvector = x0col;  // (a copy: its storage is its own)
+    HostVectorD theta(1, out.lambda_min), r, xn;
+    (void)residual_and_norms(A(out.eigenvector), out.eigenvector, out.eigenvector, theta, r, xn);
+    out.lambda_min_safe = out.lambda_min - r(0) / xn(0);
+    out.lower_bound = out.f + 1.5 * (double)N_ * std::min(out.lambda_min_safe, 0.0);
+    out.iterations = iters;
+    out.converged = nc == nev;
+    out.certified = out.converged && out.lambda_min_safe >= -out.eta;
+    return out;
   }
   // 3x3 block-Jacobi; valid after the first quadratic_model() call (TNT calls QM before precon)
   template <typename... Args>
