@@ -120,7 +120,10 @@ enum {
  * NO_ZERO_COPY, NO_GRAM_HALF, NO_UPDATE_PAIR, SO3_NO_QUAT, SO3_NO_RQUAT, SO3_SORT_NBR, HALO_RPRIME, TWO_KERNEL_STEP, WIDE_QUAD,
  * NO_POLLED_SYNC, WARN_GENERIC, REANCHOR, NO_SPMM_SWEEP, SWEEP_ZSEGS, WIDE_WINDOW, EARLY_S, DEFER_S, NO_FUSED_OBSERVER (DESIGN.md / INTEGRATION.md say what each selects).  For the boolean switches a value that
  * is not an integer counts as 1 unless it is "no" / "false" / "off"; the integer-valued ones (MAX_GRID, IPC_TIMEOUT_MS,
- * WIDE_QUAD, WIDE_WINDOW, SO3_SORT_NBR, REANCHOR, SWEEP_ZSEGS) take integers only -- anything else is ignored with a warning and the default stays.  Any other
+ * WIDE_QUAD, WIDE_WINDOW, SO3_SORT_NBR, REANCHOR, SWEEP_ZSEGS) take integers only -- anything else is ignored with a warning and the default stays.
+ * WORDS16 is ON by default (the one-pass Stiefel Hessian streams a matrix with at most 32 table values as 16-bit
+ * window words: same bits, fewer bytes); WORDS16=0 keeps the 4-byte words, and it takes integers only as well.  A
+ * context with TWO_KERNEL_STEP set keeps the 4-byte words whatever WORDS16 says.  Any other
  * MI355OPT_* variable found in the environment (a removed or misspelt switch) gets one warning on stderr.  mi_ctx_set_option changes one on a live context (name with or without the MI355OPT_
  * prefix); format switches (NO_PACKED) act when a matrix is created, the communication ones before the layer they
  * concern is brought up.  Nothing else in the library reads the environment. */
@@ -710,6 +713,12 @@ MI_API int mi_debug_window_runs(int ntiles, int max_wgs, int num_cu, size_t far_
  *               wanted, halo exchange first, Gram reduction first, the gram_count = -2 form exists}
  * A combination the library treats as an internal error is an error here too (MI_ERR_INVALID_ARGUMENT). */
 MI_API int mi_debug_stiefel_hess_form(int p, int gram_count, const size_t traits[9], const int switches[9], int out[14]);
+/* host-only, read-only: the same `out` for a matrix on a context as both stand -- what the library itself reads of them
+ * (a context that has opted into TWO_KERNEL_STEP counts as WORDS16 = 0), so FAR = 2 says that this context's Hessian
+ * pass streams the 16-bit words */
+MI_API int mi_debug_stiefel_hess_form_of(const mi_ctx *ctx, const mi_csr *A, int p, int gram_count, int out[14]);
+/* host-only: Config::words16 of a context created with MI355OPT_WORDS16 = text (NULL: unset); needs no GPU */
+MI_API int mi_debug_words16_option(const char *text, int *on);
 MI_API int mi_debug_set_rank(mi_ctx *ctx, int world_size, int rank);
 MI_API int mi_debug_csr_set_halo(mi_csr *A, int p, const double *halo_rows_host); /* (need_lo+need_hi) x p */
 /* Measurement hook: average microseconds of `reps` back-to-back applications of the operator in the fused form

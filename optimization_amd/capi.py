@@ -299,6 +299,16 @@ def stiefel_hess_form(p, gram_count, traits, switches):
     return list(out) if st == MI_OK else None
 
 
+def words16_option(text=None):
+    """mi_debug_words16_option (host-only): Config::words16 of a context created with MI355OPT_WORDS16=text (None: unset)"""
+    fn = load().mi_debug_words16_option
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+    on = C.c_int(-1)
+    check(fn(None if text is None else text.encode(), C.byref(on)))
+    return bool(on.value)
+
+
 def csr_shard_plan(n_global, world_size, rank, row_starts, col_global):
     """Host-only (no GPU): (col_local int32, need_lo, need_hi) for this rank's slab of a row-sharded matrix."""
     L = load()
@@ -995,6 +1005,16 @@ class Csr:
         check(self.L.mi_debug_csr_format_info(self.h, out))
         zidx = None if out[2] == C.c_size_t(-1).value else int(out[2])
         return dict(packed=bool(out[0]), ntable=int(out[1]), zidx=zidx, wk16=bool(out[3]), far_stride=int(out[4]))
+
+    def stiefel_hess_form(self, p, gram_count=-1):
+        """mi_debug_stiefel_hess_form_of: the 14 numbers of the one-pass Hessian's launch plan for this matrix on its
+        context as both stand (index 6, FAR: 2 = the 16-bit window words), or None where the library answers with an
+        error"""
+        fn = self.L.mi_debug_stiefel_hess_form_of
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        out = (C.c_int * 14)()
+        return list(out) if fn(self.ctx.h, self.h, p, gram_count, out) == MI_OK else None
 
     def debug_set_halo(self, p, rows):
         rows = np.ascontiguousarray(rows, dtype=np.float64)

@@ -280,7 +280,7 @@ const OptionDesc kOptions[] = {
     {"FORCE_UNIFORM_GRID", opt_force_uniform_grid}, {"IPC_TIMEOUT_MS", opt_ipc_timeout_ms, true},
     {"NO_FOLD", opt_no_fold}, {"HALO_PUSH_LATE", opt_halo_push_late}, {"NO_PACKED", opt_no_packed},
     {"NO_WINDOW", opt_no_window}, {"NO_WIN_BOUNDS", opt_no_win_bounds}, {"NO_FAR_COMPUTED", opt_no_far_computed},
-    {"WORDS16", opt_words16}, {"NO_SPMM_STREAM", opt_no_spmm_stream}, {"NO_SPMM_WIN", opt_no_spmm_win},
+    {"WORDS16", opt_words16, true}, {"NO_SPMM_STREAM", opt_no_spmm_stream}, {"NO_SPMM_WIN", opt_no_spmm_win},
     {"NO_SPMM_SWEEP", opt_no_spmm_sweep}, {"SWEEP_ZSEGS", opt_sweep_zsegs, true},
     {"NO_ZERO_COPY", opt_no_zero_copy}, {"NO_POLLED_SYNC", opt_no_polled_sync}, {"WIDE_QUAD", opt_wide_quad, true}, {"WIDE_WINDOW", opt_wide_window, true},
     {"NO_UPDATE_MFMA", opt_no_update_mfma}, {"HALO_RPRIME", opt_halo_rprime}, {"NO_GRAM_HALF", opt_no_gram_half}, {"SO3_NO_QUAT", opt_so3_no_quat}, {"SO3_NO_RQUAT", opt_so3_no_rquat}, {"EARLY_S", opt_early_s}, {"DEFER_S", opt_defer_s}, {"NO_FUSED_OBSERVER", opt_no_fused_observer}, {"NO_FUSED_LSQR_OBSERVER", opt_no_fused_lsqr_observer}, {"NO_UPDATE_PAIR", opt_no_update_pair}, {"TWO_KERNEL_STEP", opt_two_kernel_step}, {"SO3_SORT_NBR", opt_so3_sort_nbr, true},
@@ -290,6 +290,8 @@ const OptionDesc kOptions[] = {
 // the r01-r03 scripts) means 1, so that no spelling that used to switch something on is silently off.  An INTEGER-valued
 // option (MAX_GRID, IPC_TIMEOUT_MS, WIDE_QUAD, SO3_SORT_NBR) takes integers only: `MI355OPT_IPC_TIMEOUT_MS=` or `=yes`
 // used to mean a 1 ms timeout and `MI355OPT_MAX_GRID=` one workgroup -- now a warning, and the default stays.
+// WORDS16 is on by default and takes integers only too (0: off): for a switch that is on, "anything else means 1" would
+// turn `=off` into off and `=disabled` into on.
 bool option_value(const OptionDesc &o, const char *e, long *v) {
   char *end = nullptr;
   *v = strtol(e, &end, 0);
@@ -367,6 +369,18 @@ int mi_ctx_set_option(mi_ctx *ctx, const char *name, long value) {
     if (strcmp(o.name, name) == 0) return o.set(ctx, value);
   set_error("unknown option '%s'", name);
   return MI_ERR_INVALID_ARGUMENT;
+}
+
+// Host-only: what Config::words16 of a new context is when MI355OPT_WORDS16 holds `text` (null: unset) -- the default
+// and the option's own parsing (option_value, the setter) on a context that never sees a device
+int mi_debug_words16_option(const char *text, int *on) {
+  MI_REQUIRE(on, "null argument");
+  mi_ctx scratch;
+  long v = 0;
+  for (const OptionDesc &o : kOptions)
+    if (strcmp(o.name, "WORDS16") == 0 && text && option_value(o, text, &v)) (void)o.set(&scratch, v);
+  *on = scratch.cfg.words16;
+  return MI_OK;
 }
 
 int mi_device_count(int *count) {

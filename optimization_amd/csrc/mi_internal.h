@@ -146,7 +146,7 @@ struct Config {
   bool no_window = false;           // NO_WINDOW: the one-pass Hessian in streaming form
   bool no_win_bounds = false;       // NO_WIN_BOUNDS: equal runs instead of the planned ones (window kernels)
   bool no_far_computed = false;     // NO_FAR_COMPUTED: far columns loaded from wfar
-  bool words16 = false;             // WORDS16: 16-bit window words (opt-in)
+  bool words16 = true;              // WORDS16: 16-bit window words where the matrix has them; 0: 4-byte words
   bool no_spmm_stream = false;      // NO_SPMM_STREAM: the straight sparse core instead of the pipelined one
   bool no_spmm_sweep = true;        // NO_SPMM_SWEEP: the LOBPCG panel product of a pure-far-structure matrix keeps the window
                                     // form (r06: the plane-sweep form is opt-in until it measures faster: NO_SPMM_SWEEP=0)

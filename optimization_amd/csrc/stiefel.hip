@@ -1307,11 +1307,17 @@ struct StHessTraits {
   bool no_window, no_far_computed, words16, no_win_bounds, uniform_grid, slot_mode, twok_r;
   int wide_quad, wide_window;
 };
-StHessTraits st_hess_traits(const mi_ctx *ctx, const mi_csr *A) {
+// `two_kernel_step`: the context has opted into the two-kernel step (Config::two_kernel_step).  That experiment's Hessian
+// pass exists for 4-byte words only, so such a context keeps them; the 16-bit words are every other context's default.
+StHessTraits st_hess_traits(const mi_ctx *ctx, const mi_csr *A, bool two_kernel_step) {
   const Config &c = ctx->cfg;
   return {A->pk != nullptr, A->wk != nullptr, A->wk16 != nullptr, A->win_chunks, A->win_head, A->win_far_pure,
-          A->win_far_stride, A->halo != nullptr, csr_row_sharded(A), c.no_window, c.no_far_computed, c.words16,
-          c.no_win_bounds, ctx->uniform_grid, slot_mode(ctx), ctx->twok_r != nullptr, c.wide_quad, c.wide_window};
+          A->win_far_stride, A->halo != nullptr, csr_row_sharded(A), c.no_window, c.no_far_computed,
+          c.words16 && !two_kernel_step, c.no_win_bounds, ctx->uniform_grid, slot_mode(ctx), ctx->twok_r != nullptr,
+          c.wide_quad, c.wide_window};
+}
+StHessTraits st_hess_traits(const mi_ctx *ctx, const mi_csr *A) {
+  return st_hess_traits(ctx, A, ctx->cfg.two_kernel_step);
 }
 
 struct StHessPlan {
@@ -1367,8 +1373,9 @@ int st_hess_plan(int p, int gram_count, const StHessTraits &t, StHessPlan *out) 
   // the window form when the matrix qualifies (decided at creation, sparse.hip build_window); p = 4 does not fit
   pl.wc = (t.no_window || p > 3 || !t.wk) ? 0 : t.win_chunks;
   const bool win = pl.recur && pl.wc > 0;  // (recurrence form only: the unpreconditioned solve)
-  // 16-bit words: opt-in (MI355OPT_WORDS16=1).  On cfg2 they shorten the pass by ~1 us (25.9 -> 24.9 us) by halving
-  // the matrix stream (28 -> 16 MB of 132 MB); the pass then runs at the same ~5.5 TB/s of a smaller total.
+  // 16-bit words: the default of a context (st_hess_traits; MI355OPT_WORDS16=0 keeps the 4-byte words) wherever the
+  // matrix has them, its far columns are computed and none of them is a halo column.  On cfg2 they shorten the pass by
+  // halving the matrix stream (28 -> 16 MB of 128 MB) at the same bits (profiles/words16_default_ab.md).
   const bool w16 = pl.fard && !t.halo && t.wk16 && t.words16;
   pl.form = win ? ST_HESS_WINDOW : ST_HESS_PLAIN, pl.block = win ? kWinBlock : kBlock;
   pl.run_table = win && !t.uniform_grid;  // planned runs of whole tiles (sparse.hip window_bounds)
@@ -1635,10 +1642,7 @@ __attribute__((visibility("default"))) int mi_debug_stamp_buffer(void *dev_ptr) 
 #endif
 
 // Host-only: the launch plan of the one-pass Hessian (st_hess_plan) for plain numbers -- see include/mi355opt.h
-int mi_debug_stiefel_hess_form(int p, int gram_count, const size_t m[9], const int s[9], int out[14]) {
-  MI_REQUIRE(m && s && out, "null argument");
-  const StHessTraits t{m[0] != 0, m[1] != 0, m[2] != 0, (int)m[3], (int)m[4], m[5], m[6], m[7] != 0, m[8] != 0,
-                       s[0] != 0, s[1] != 0, s[2] != 0, s[5] != 0, s[6] != 0, s[7] != 0, s[8] != 0, s[3], s[4]};
+static int hess_form_numbers(int p, int gram_count, const StHessTraits &t, int out[14]) {
   StHessPlan pl;
   const int st = st_hess_plan(p, gram_count, t, &pl);
   if (st != MI_OK) set_error("%s", pl.error);
@@ -1646,6 +1650,17 @@ int mi_debug_stiefel_hess_form(int p, int gram_count, const size_t m[9], const i
                      pl.run_table, pl.exchange, pl.gram_reduce, st_hess_twok_exists(p, t)};
   std::copy(v, v + 14, out);
   return st;
+}
+int mi_debug_stiefel_hess_form(int p, int gram_count, const size_t m[9], const int s[9], int out[14]) {
+  MI_REQUIRE(m && s && out, "null argument");
+  const StHessTraits t{m[0] != 0, m[1] != 0, m[2] != 0, (int)m[3], (int)m[4], m[5], m[6], m[7] != 0, m[8] != 0,
+                       s[0] != 0, s[1] != 0, s[2] != 0, s[5] != 0, s[6] != 0, s[7] != 0, s[8] != 0, s[3], s[4]};
+  return hess_form_numbers(p, gram_count, t, out);
+}
+// ... and for a matrix on a context as they stand: the plan mi_stpcg's Hessian pass would be launched by right now
+int mi_debug_stiefel_hess_form_of(const mi_ctx *ctx, const mi_csr *A, int p, int gram_count, int out[14]) {
+  MI_REQUIRE(ctx && A && out, "null argument");
+  return hess_form_numbers(p, gram_count, st_hess_traits(ctx, A), out);
 }
 
 int mi_stiefel_gram(mi_ctx *ctx, size_t n, int p, const mi_vec *X, const mi_vec *Z, double *G_host) {
@@ -1791,8 +1806,9 @@ int mi_stiefel_rq_model(mi_stiefel_rq *q, const mi_vec *X, mi_vec *grad, mi_op *
   q->dg.Y = q->Y->d;
   q->dg.S = q->S_dev;
   q->dg.halo_A = q->A->halo ? q->A : nullptr;
-  // (the opt-in two-kernel step: p = 3, window form with computed far columns, one rank)
-  q->dg.twok = st_hess_twok_exists(q->p, st_hess_traits(q->ctx, q->A));
+  // (the opt-in two-kernel step: p = 3, window form with computed far columns, one rank.  Asked for a context that HAS
+  // opted in: the switch may be set on this context after the model exists, and mi_stpcg reads it per solve)
+  q->dg.twok = st_hess_twok_exists(q->p, st_hess_traits(q->ctx, q->A, true));
   // the one-pass kernel uses 32-bit byte offsets: fields of 4 GiB or more keep the two-pass operator -- and so does
   // a matrix that is not symmetric (checked at creation): the one-pass form replaces X'(A p) by (A X)'p
   // rows of 9 ... 16 doubles have no one-pass form (st_hess_plan): STPCG drives the two-pass operator through
