@@ -111,6 +111,8 @@ enum {
   MI_K_SO3_RESIDUAL,    /* k_so3_residual: F(R) of mi_so3n_residual */
   MI_K_SO3_JAC,         /* k_so3_jac: dF xi over the edges (apply and apply_sub_scaled forms) */
   MI_K_SO3_JACT,        /* k_so3_jact: dF* y over the incidences (apply and apply_sub_scaled forms) */
+  MI_K_SO3_EDGE_WEIGHT, /* k_so3_edge_weight: the per-edge pass of mi_so3n_reweight */
+  MI_K_SO3_INC_REWEIGHT, /* k_so3_inc_reweight: the per-incidence pass of mi_so3n_reweight */
   MI_K_COUNT
 };
 /* The library's switches (A/B forms of its kernels, verification hooks of the multi-rank path) are read from the
@@ -556,6 +558,32 @@ MI_API int mi_so3n_cert_apply_blocks(mi_so3n_cert *cert, const struct mi_panel_b
 /* The 3N x 3 column-major panel Y (Y(3i + r, c) = R_i[c][r]) at the certificate's point: S Y = 0 at a critical point, so
  * these are the three eigenvectors at (or near) 0 -- the start block of an eigensolver deflates them.  Borrowed. */
 MI_API int mi_so3n_cert_null_panel(mi_so3n_cert *cert, mi_vec **Y);
+/* Robust loss by iteratively reweighted least squares: the edge weights become w_e = w0_e phi(r_e) on the device, with
+ * w0_e the creation-time weight, r_e = |R_j - R_i Rt_e|_F the UNWEIGHTED chordal residual at R, s = r_e^2 / c^2 and
+ *   MI_ROBUST_L2             phi = 1                          rho = r^2 / 2
+ *   MI_ROBUST_HUBER          phi = 1 (r <= c), c / r (r > c)  rho = r^2 / 2 (r <= c), c r - c^2 / 2 (r > c)
+ *   MI_ROBUST_CAUCHY         phi = 1 / (1 + s)                rho = (c^2 / 2) log1p(s)
+ *   MI_ROBUST_GEMAN_MCCLURE  phi = 1 / (1 + s)^2              rho = (r^2 / 2) / (1 + s)
+ * (rho' = r phi: a minimiser of sum w0 rho(r) is a fixed point of solve / reweight rounds).  Graduated non-convexity with
+ * the Geman-McClure surrogate, w = (mu c^2 / (r^2 + mu c^2))^2, is MI_ROBUST_GEMAN_MCCLURE called with c sqrt(mu): it needs
+ * no kind of its own.  Two passes, no atomics (the same bits on every run): one thread per edge, then one lane per node
+ * rewriting the per-incidence weights (and, where they exist, sqrt(w_e) of the least-squares view and the diagonal of
+ * mi_so3n_gn_scaling).  Every entry point of this section then computes what a problem created with the weights
+ * mi_so3n_weights returns computes.
+ * w_e <- w0_e * phi(|R_j - R_i Rt_e|_F ; kind, c).  info (nullable) = {sum w0 rho(r), sum w r^2/2, #edges with phi < 1/2}:
+ * one read-back (sync); info == NULL: no sync.  R may be NULL for MI_ROBUST_L2 (restores the creation-time weights; info is
+ * then formed with r = 0).  The first call uploads the creation-time weights, the per-edge streams and the incidence -> edge
+ * map (sync).
+ * A reweighting drops the bound model, the speculative model of the last mi_so3n_trial and the gradient of the last
+ * mi_so3n_armijo_trial: a following mi_so3n_model on any vector assembles afresh, and mi_so3n_trial needs a new
+ * mi_so3n_model first.  The handle of mi_so3n_certificate and the pair of mi_so3n_jacobian were formed with the old weights
+ * and must be requested again; the handle of mi_so3n_gn_scaling stays valid and sees the new scaling.
+ * MI_ERR_INVALID_ARGUMENT (weights untouched): an unknown kind; c not finite or <= 0 for a kind other than MI_ROBUST_L2; R
+ * of the wrong length or context, or NULL for such a kind; a context with a communicator (single-context only).
+ * n_edges = 0 is allowed (info = 0). */
+enum { MI_ROBUST_L2 = 0, MI_ROBUST_HUBER = 1, MI_ROBUST_CAUCHY = 2, MI_ROBUST_GEMAN_MCCLURE = 3 };
+MI_API int mi_so3n_reweight(mi_so3n *prob, const mi_vec *R, int kind, double c, double info[3]);
+MI_API int mi_so3n_weights(mi_so3n *prob, double *w_host /* E */);   /* sync: the current w_e */
 
 /* ---------------------------------------------------------------------------------------------
  * (8) LOBPCG building blocks (LinearAlgebra/LOBPCG.h:131-337).  Panels are column-major m x k

@@ -18,7 +18,8 @@ STATUS = {0: "MI_OK", 1: "MI_ERR_INVALID_ARGUMENT", 2: "MI_ERR_HIP", 3: "MI_ERR_
 KERNELS = ["none", "cg_init", "cg_dot3", "cg_scalar_a", "cg_update", "cg_scalar_b", "cg_pupdate",
            "csr_spmm", "stiefel_spmm_gram", "stiefel_gram_reduce", "stiefel_finish_dots",
            "stiefel_retract", "bsr3_spmv_dots", "blas1", "lobpcg_gram", "lobpcg_update",
-           "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo", "so3_grad"]
+           "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo", "so3_grad",
+           "so3_residual", "so3_jac", "so3_jact", "so3_edge_weight", "so3_inc_reweight"]
 KID = {k: i for i, k in enumerate(KERNELS)}
 STPCG_EXIT = ["RESIDUAL", "MAXIT", "KERNEL", "BOUNDARY", "USER"]
 
@@ -208,6 +209,8 @@ def load():
         "mi_so3n_cert_apply": [vp, C.c_int, vp, vp],
         "mi_so3n_cert_apply_blocks": [vp, C.POINTER(PanelBlocks), vp],
         "mi_so3n_cert_null_panel": [vp, C.POINTER(vp)],
+        "mi_so3n_reweight": [vp, vp, C.c_int, C.c_double, c_double_p],
+        "mi_so3n_weights": [vp, c_double_p],
         "mi_stpcg_collect": [vp, C.POINTER(StpcgResult)],
         "mi_lobpcg_gram": [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, c_double_p],
         "mi_lobpcg_update": [vp, C.c_size_t, C.c_int, C.c_int, vp, c_double_p, C.c_int, vp],
@@ -1212,6 +1215,22 @@ class So3N:
         out = np.zeros(3)
         check(self.L.mi_so3n_certificate(self.h, R.h, C.byref(h), _dp(out)))
         return So3NCertificate(self, h), dict(f=out[0], stationarity=out[1], trace_C=out[2])
+
+    ROBUST = {"l2": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
+
+    def reweight(self, R, kind, c, info=True):
+        """mi_so3n_reweight: w_e <- w0_e phi(|R_j - R_i Rt_e|_F; kind, c), kind a name of So3N.ROBUST or its number; R may
+        be None for "l2".  info: dict(robust_cost, weighted_cost, outliers) from one read-back; info=False: None, no sync"""
+        out = np.zeros(3)
+        check(self.L.mi_so3n_reweight(self.h, R.h if R is not None else None, int(self.ROBUST.get(kind, kind)), float(c),
+                                      _dp(out) if info else None))
+        return dict(robust_cost=out[0], weighted_cost=out[1], outliers=int(out[2])) if info else None
+
+    def weights(self):
+        """mi_so3n_weights: the current edge weights (E doubles, the caller's edge order)"""
+        w = np.zeros(self.E)
+        check(self.L.mi_so3n_weights(self.h, _dp(w)))
+        return w
 
     def armijo_trial(self, R, g, t, h=None, R_trial=None):
         """mi_so3n_armijo_trial: (h = -t g Vec, R_trial Vec, dict(f, grad_sqnorm))"""

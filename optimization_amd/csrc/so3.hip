@@ -591,6 +591,104 @@ __global__ __launch_bounds__(kNlsBlock) void k_so3_jact(IncView inc, const doubl
   if (FUSED) block_partials_store_nw<1, kNlsBlock / 64>(acc, lds, partials);
 }
 
+// ---- robust loss by edge reweighting (mi_so3n_reweight) ---------------------------------------------------
+//     w_e = w0_e phi(r_e),  r_e = |R_j - R_i Rt_e|_F (unweighted),  s = r_e^2 / c^2,  rho' = r phi
+//     L2: phi = 1, rho = r^2 / 2;  Huber: phi = 1 | c / r, rho = r^2 / 2 | c r - c^2 / 2 (r <= c | r > c);
+//     Cauchy: phi = 1 / (1 + s), rho = (c^2 / 2) log1p(s);  Geman-McClure: phi = 1 / (1 + s)^2, rho = (r^2 / 2) / (1 + s)
+// k_so3_edge_weight: one thread per edge in the caller's order on the grid of edge_grid(), the loaders of k_so3_residual; the
+// rotations always as the 72-byte rows of R (once per robust round: one form is enough); rot == nullptr: r = 0 (L2 restoring
+// the creation-time weights needs no point).  Writes w_e, sqrt(w_e) into swe when the least-squares arrays exist, and
+// three partial rows per workgroup (components 0..2 of `partials`, reduced as the residual's row): sum w0 rho(r), sum w r^2 / 2,
+// the number of edges with phi < 1/2.  No atomics.
+// Algorithmic bytes: 8 E (end points) + 8 E (w0) + 32 (72) E measurement + 144 E rotations + 8 E written [+ 8 E: swe]
+//                                                                                                  = 200 (240) E [+ 8 E]
+enum { SO3_ROBUST_L2 = 0, SO3_ROBUST_HUBER = 1, SO3_ROBUST_CAUCHY = 2, SO3_ROBUST_GM = 3 };
+template <bool SQ>
+__global__ __launch_bounds__(kNlsBlock) void k_so3_edge_weight(EdgeView ev, const double *__restrict__ w0,
+                                                               const double *__restrict__ rot, int kind, double c,
+                                                               double *__restrict__ w, double *__restrict__ swe,
+                                                               double *__restrict__ partials) {
+  __shared__ double lds[3 * (kNlsBlock / 64)];
+  double acc[3] = {0, 0, 0};
+  const double c2 = c * c;
+  const size_t stride = (size_t)gridDim.x * kNlsBlock;
+  for (size_t e = (size_t)blockIdx.x * kNlsBlock + threadIdx.x; e < ev.E; e += stride) {
+    double r2 = 0;
+    if (rot) {
+      const int2 ij = ev.ij[e];
+      double Ri[9], Rj[9], S[9], RiS[9];
+      load_rot<false>(rot, (size_t)ij.x, Ri);
+      load_rot<false>(rot, (size_t)ij.y, Rj);
+      load_edge_meas<SQ>(ev, e, S);
+      mat3_mul(Ri, S, RiS);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const double d = Rj[k] - RiS[k];
+        r2 += d * d;
+      }
+    }
+    double phi = 1.0, rho = .5 * r2;
+    if (kind == SO3_ROBUST_HUBER) {
+      const double r = sqrt(r2);
+      if (r > c) {
+        phi = c / r;
+        rho = c * r - .5 * c2;
+      }
+    } else if (kind == SO3_ROBUST_CAUCHY) {
+      const double s = r2 / c2;
+      phi = 1.0 / (1.0 + s);
+      rho = .5 * c2 * log1p(s);
+    } else if (kind == SO3_ROBUST_GM) {
+      const double s = r2 / c2, t = 1.0 / (1.0 + s);
+      phi = t * t;
+      rho = .5 * r2 * t;
+    }
+    const double w0e = w0[e], we = w0e * phi;
+    w[e] = we;
+    if (swe) swe[e] = sqrt(we);
+    acc[0] += w0e * rho;
+    acc[1] += we * (.5 * r2);
+    acc[2] += phi < .5 ? 1.0 : 0.0;
+  }
+  block_partials_store_nw<3, kNlsBlock / 64>(acc, lds, partials);
+}
+// swe = sqrt(w): the least-squares view first asked for after a reweighting (nls_upload)
+__global__ __launch_bounds__(kNlsBlock) void k_so3_sqrt_w(size_t E, const double *__restrict__ w, double *__restrict__ swe) {
+  const size_t stride = (size_t)gridDim.x * kNlsBlock;
+  for (size_t e = (size_t)blockIdx.x * kNlsBlock + threadIdx.x; e < E; e += stride) swe[e] = sqrt(w[e]);
+}
+// k_so3_inc_reweight: the per-incidence weight stream from the per-edge weights, winc[slot] = w[slot_edge[slot] >> 1], one
+// lane per node on the walk of k_so3_jact.  Only OCCUPIED slots are written: a padding slot keeps its weight 0 (its word is
+// 0, which reads as edge 0).  What tells them apart is static and streamed already: a padding slot's neighbour is the lane's
+// own node, and no edge joins a node to itself (mi_so3n_create refuses one); the padding lanes of the last slice own no node.
+// gn (nullable): the Gauss-Newton scaling 1 / sqrt(2 degw_i), each three times, degw_i summed in slot order (1 for degw_i = 0).
+// Algorithmic bytes: nnzb (4 neighbour + 4 word + 8 gathered + 8 written) + 4 N [+ 24 N: gn] = 48 E + 4 N [+ 24 N]
+__global__ __launch_bounds__(kNlsBlock) void k_so3_inc_reweight(IncView inc, const uint32_t *__restrict__ slot_edge,
+                                                                const double *__restrict__ w, double *__restrict__ winc,
+                                                                double *__restrict__ gn) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const size_t ngroups = (inc.nslices + 3) / 4;
+  for (size_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const size_t slice = grp * 4 + wv;
+    if (slice >= inc.nslices) continue;
+    const int node = inc.perm[slice * 64 + lane];
+    if (node < 0) continue;
+    double degw = 0;
+    const long long b0 = inc.slice_ptr[slice], b1 = inc.slice_ptr[slice + 1];
+    for (long long k = b0; k < b1; ++k) {
+      const size_t e0 = (size_t)k * 64 + lane;
+      if (inc.nbr[e0] == node) continue;
+      const double we = w[(size_t)(slot_edge[e0] >> 1)];
+      winc[e0] = we;
+      degw += we;
+    }
+    if (gn) {
+      const double d = degw > 0 ? 1.0 / sqrt(2 * degw) : 1.0;
+      gn[3 * (size_t)node] = d; gn[3 * (size_t)node + 1] = d; gn[3 * (size_t)node + 2] = d;
+    }
+  }
+}
+
 // ---- global-optimality certificate -----------------------------------------------------------------------
 // With Y in R^{3N x 3}, Y_i = R_i', and the 3N x 3N connection Laplacian (diagonal blocks degw_i I, block (i, j) = -w_e Rt_e
 // and (j, i) = -w_e Rt_e' for e = (i -> j)), f(R) = const + 1/2 tr(Y' Lap Y), and the certificate matrix at R is
@@ -847,6 +945,9 @@ struct mi_so3n {
   mi_vec *gn_diag = nullptr;        // 3N: 1 / sqrt(2 degw_i), each three times
   mi_op *gn_op = nullptr;
   mi_so3n_cert *cert = nullptr;     // mi_so3n_certificate: owned here, rebound by every call
+  // ---- mi_so3n_reweight: device, E each, from the first reweighting on.  w_cur != nullptr <=> the weights in force are
+  // w_cur (what winc, swe and gn_diag were last written from), not h_w: every later first-use path reads it
+  double *w0 = nullptr, *w_cur = nullptr;
 };
 
 namespace {
@@ -1138,6 +1239,7 @@ int mi_so3n_destroy(mi_so3n *q) {
   mi_vec_destroy(q->Hh);
   mi_vec_destroy(q->Pg);
   (void)hipFree(q->e_ij); (void)hipFree(q->Se); (void)hipFree(q->swe); (void)hipFree(q->slot_edge); (void)hipFree(q->Jrot);
+  (void)hipFree(q->w0); (void)hipFree(q->w_cur);
   if (q->gn_op) {
     q->gn_op->borrowed = false;
     mi_op_destroy(q->gn_op);
@@ -1336,29 +1438,56 @@ int mi_so3n_armijo_trial(mi_so3n *q, const mi_vec *R, const mi_vec *g, double t,
 
 namespace {
 
-// the edge streams of the least-squares view, on first use
-int nls_upload(mi_so3n *q, bool with_slots) {
-  MI_REQUIRE(q->w_nonneg, "the least-squares form F_e = sqrt(w_e) (R_j - R_i Rt_e) needs weights >= 0");
-  MI_REQUIRE(!q->ctx->uniform_grid, "the least-squares view of mi_so3n is single-context");
-  if (!q->e_ij) {
-    std::vector<double> sw(q->E);
-    for (size_t e = 0; e < q->E; ++e) sw[e] = std::sqrt(q->h_w[e]);
-    MI_TRY(upload((void **)&q->Se, q->h_Se.data(), q->h_Se.size() * sizeof(double)));
-    MI_TRY(upload((void **)&q->swe, sw.data(), sw.size() * sizeof(double)));
-    MI_TRY(upload((void **)&q->e_ij, q->h_ij.data(), q->h_ij.size() * sizeof(int32_t)));
-  }
-  if (with_slots && !q->slot_edge) {
-    MI_REQUIRE(q->E < ((size_t)1 << 31), "the incidence -> edge words hold edge numbers below 2^31");
-    MI_TRY(upload((void **)&q->slot_edge, q->h_slot.data(), q->h_slot.size() * sizeof(uint32_t)));
-    MI_HIP(hipMalloc((void **)&q->Jrot, q->N * 9 * sizeof(double)));
-  }
-  return MI_OK;
-}
-EdgeView edge_view(const mi_so3n *q) { return EdgeView{q->E, q->e_ij, q->Se, q->swe}; }
 int edge_grid(const mi_so3n *q) {
   return (int)std::min<size_t>(std::max<size_t>(1, (q->E + kNlsBlock - 1) / kNlsBlock), (size_t)kMaxRows);
 }
 int node_grid(const mi_so3n *q) { return (int)std::min<size_t>(std::max<size_t>(1, (q->nslices + 3) / 4), (size_t)kMaxRows); }
+// the static per-edge streams (end points, measurement) and the incidence -> edge words, on first use
+int edge_upload(mi_so3n *q) {
+  if (q->e_ij) return MI_OK;
+  MI_TRY(upload((void **)&q->Se, q->h_Se.data(), q->h_Se.size() * sizeof(double)));
+  MI_TRY(upload((void **)&q->e_ij, q->h_ij.data(), q->h_ij.size() * sizeof(int32_t)));
+  return MI_OK;
+}
+int slot_upload(mi_so3n *q) {
+  if (q->slot_edge) return MI_OK;
+  MI_REQUIRE(q->E < ((size_t)1 << 31), "the incidence -> edge words hold edge numbers below 2^31");
+  return upload((void **)&q->slot_edge, q->h_slot.data(), q->h_slot.size() * sizeof(uint32_t));
+}
+// the edge streams of the least-squares view, on first use; sqrt(w_e) from the weights in force (after a reweighting: the
+// device's, mi_so3n::w_cur)
+int nls_upload(mi_so3n *q, bool with_slots) {
+  MI_REQUIRE(q->w_nonneg, "the least-squares form F_e = sqrt(w_e) (R_j - R_i Rt_e) needs weights >= 0");
+  MI_REQUIRE(!q->ctx->uniform_grid, "the least-squares view of mi_so3n is single-context");
+  MI_TRY(edge_upload(q));
+  if (!q->swe) {
+    if (q->w_cur) {
+      MI_HIP(hipMalloc((void **)&q->swe, std::max<size_t>(1, q->E) * sizeof(double)));
+      hipLaunchKernelGGL(k_so3_sqrt_w, dim3(edge_grid(q)), dim3(kNlsBlock), 0, q->ctx->stream, q->E, (const double *)q->w_cur,
+                         q->swe);
+      MI_HIP(hipGetLastError());
+    } else {
+      std::vector<double> sw(q->E);
+      for (size_t e = 0; e < q->E; ++e) sw[e] = std::sqrt(q->h_w[e]);
+      MI_TRY(upload((void **)&q->swe, sw.data(), sw.size() * sizeof(double)));
+    }
+  }
+  if (with_slots) {
+    MI_TRY(slot_upload(q));
+    if (!q->Jrot) MI_HIP(hipMalloc((void **)&q->Jrot, q->N * 9 * sizeof(double)));
+  }
+  return MI_OK;
+}
+// winc (and gn_diag when it exists) from the per-edge weights w_cur
+int launch_inc_reweight(mi_so3n *q) {
+  mi_ctx *ctx = q->ctx;
+  KScope ks(ctx, MI_K_SO3_INC_REWEIGHT);
+  hipLaunchKernelGGL(k_so3_inc_reweight, dim3(node_grid(q)), dim3(kNlsBlock), 0, ctx->stream, view(q),
+                     (const uint32_t *)q->slot_edge, (const double *)q->w_cur, q->winc, q->gn_diag ? q->gn_diag->d : nullptr);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+EdgeView edge_view(const mi_so3n *q) { return EdgeView{q->E, q->e_ij, q->Se, q->swe}; }
 
 int so3_jac_launch(mi_op *self, const mi_vec *in, mi_vec *out, const double *scale, const int *mode, const int *gate,
                    double *partials, int *nparts) {
@@ -1474,18 +1603,80 @@ int mi_so3n_gn_scaling(mi_so3n *q, mi_op **M) {
   SO3_REQUIRE_ARGS(q && M);
   MI_REQUIRE(q->w_nonneg, "the Gauss-Newton scaling 1 / sqrt(2 degw) needs weights >= 0");
   if (!q->gn_op) {
-    std::vector<double> degw(q->N, 0.0), d(3 * q->N);
-    for (size_t e = 0; e < q->E; ++e) {
-      degw[(size_t)q->h_ij[2 * e]] += q->h_w[e];
-      degw[(size_t)q->h_ij[2 * e + 1]] += q->h_w[e];
-    }
-    for (size_t i = 0; i < q->N; ++i) d[3 * i] = d[3 * i + 1] = d[3 * i + 2] = degw[i] > 0 ? 1.0 / std::sqrt(2 * degw[i]) : 1.0;
     MI_TRY(mi_vec_create(q->ctx, 3 * q->N, &q->gn_diag));
-    MI_TRY(mi_vec_upload(q->gn_diag, d.data(), d.size()));
+    if (q->w_cur) {
+      // after a reweighting: from the weights in force, by the pass that keeps it current (winc is rewritten to itself)
+      touch(q->gn_diag);
+      MI_TRY(launch_inc_reweight(q));
+    } else {
+      std::vector<double> degw(q->N, 0.0), d(3 * q->N);
+      for (size_t e = 0; e < q->E; ++e) {
+        degw[(size_t)q->h_ij[2 * e]] += q->h_w[e];
+        degw[(size_t)q->h_ij[2 * e + 1]] += q->h_w[e];
+      }
+      for (size_t i = 0; i < q->N; ++i) d[3 * i] = d[3 * i + 1] = d[3 * i + 2] = degw[i] > 0 ? 1.0 / std::sqrt(2 * degw[i]) : 1.0;
+      MI_TRY(mi_vec_upload(q->gn_diag, d.data(), d.size()));
+    }
     MI_TRY(mi_op_create_diag(q->ctx, q->gn_diag, &q->gn_op));
     q->gn_op->borrowed = true;
   }
   *M = q->gn_op;
+  return MI_OK;
+}
+
+// ---- robust loss by edge reweighting (kernels: k_so3_edge_weight, k_so3_inc_reweight) ----
+int mi_so3n_reweight(mi_so3n *q, const mi_vec *R, int kind, double c, double info[3]) {
+  SO3_REQUIRE_ARGS(q);
+  mi_ctx *ctx = q->ctx;
+  MI_REQUIRE(kind >= SO3_ROBUST_L2 && kind <= SO3_ROBUST_GM, "unknown robust kernel %d", kind);
+  MI_REQUIRE(kind == SO3_ROBUST_L2 || (std::isfinite(c) && c > 0), "the robust scale c must be finite and > 0");
+  MI_REQUIRE(R || kind == SO3_ROBUST_L2, "R may be null only for MI_ROBUST_L2");
+  MI_REQUIRE(!R || (R->ctx == q->ctx && R->n == 9 * q->N), "R must hold N row-major 3x3 blocks");
+  MI_REQUIRE(!ctx->uniform_grid, "the reweighting of mi_so3n is single-context");
+  if (kind == SO3_ROBUST_L2) c = 1.0;
+  // what was worked out with the old weights: the bound model, the speculative trial model, the Armijo gradient (the rq
+  // key describes a point, not the weights, and stays)
+  q->R = nullptr;
+  q->R_serial = 0;
+  q->trial.clear();
+  q->armijo.clear();
+  if (q->E == 0) {
+    if (info) info[0] = info[1] = info[2] = 0.0;
+    return MI_OK;
+  }
+  if (!q->w_cur) {  // first use: the one-time uploads (sync)
+    MI_TRY(edge_upload(q));
+    MI_TRY(slot_upload(q));
+    MI_TRY(upload((void **)&q->w0, q->h_w.data(), q->E * sizeof(double)));
+    MI_HIP(hipMalloc((void **)&q->w_cur, q->E * sizeof(double)));
+  }
+  const int grid = edge_grid(q);
+  {
+    KScope ks(ctx, MI_K_SO3_EDGE_WEIGHT);
+    DISPATCH_FLAG(q->sinc_quat, SQ,
+        hipLaunchKernelGGL((k_so3_edge_weight<SQ>), dim3(grid), dim3(kNlsBlock), 0, ctx->stream, edge_view(q),
+                           (const double *)q->w0, R ? (const double *)R->d : (const double *)nullptr, kind, c, q->w_cur,
+                           q->swe, ctx->partials2));
+  }
+  MI_HIP(hipGetLastError());
+  if (q->gn_diag) touch(q->gn_diag);
+  MI_TRY(launch_inc_reweight(q));
+  if (info) {
+    MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, grid, 3, ctx->scalars + SLOT_MISC));
+    MI_TRY(read_slots_sync(ctx, SLOT_MISC, 3, info));  // the one read-back
+  }
+  return MI_OK;
+}
+
+int mi_so3n_weights(mi_so3n *q, double *w_host) {
+  SO3_REQUIRE_ARGS(q && (w_host || q->E == 0));
+  if (q->E == 0) return MI_OK;
+  if (!q->w_cur) {
+    std::memcpy(w_host, q->h_w.data(), q->E * sizeof(double));
+    return MI_OK;
+  }
+  MI_TRY(stream_wait(q->ctx, "mi_so3n_weights"));
+  MI_HIP(hipMemcpy(w_host, q->w_cur, q->E * sizeof(double), hipMemcpyDeviceToHost));
   return MI_OK;
 }
 

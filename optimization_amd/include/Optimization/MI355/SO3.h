@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdint>
 #include <optional>
+#include <vector>
 
 #include "Optimization/LinearAlgebra/Concepts.h"
 #include "Optimization/LinearAlgebra/LOBPCG.h"
@@ -71,6 +72,18 @@ struct CertifyResult {
   double eta = 0;              // the threshold used
   size_t iterations = 0;
   bool converged = false, certified = false;
+};
+
+// A robust loss for RotationAveraging::reweight (mi355opt.h: mi_so3n_reweight): the weight function phi(r; c) applied to
+// the creation-time weights.  GNC with the Geman-McClure surrogate: {GemanMcClure, c * std::sqrt(mu)}.
+struct RobustKernel {
+  enum Kind { L2 = MI_ROBUST_L2, Huber = MI_ROBUST_HUBER, Cauchy = MI_ROBUST_CAUCHY, GemanMcClure = MI_ROBUST_GEMAN_MCCLURE } kind = L2;
+  double c = 1;
+};
+struct ReweightInfo {
+  double robust_cost = 0;    // sum_e w0_e rho(r_e)
+  double weighted_cost = 0;  // sum_e w_e r_e^2 / 2 with the NEW weights: the objective at the same point
+  size_t outliers = 0;       // edges with phi < 1/2
 };
 
 class RotationAveraging {
@@ -266,6 +279,30 @@ class RotationAveraging {
     out.converged = nc == nev;
     out.certified = out.converged && out.lambda_min_safe >= -out.eta;
     return out;
+  }
+  // --- robust loss -------------------------------------------------------------------------------------------------
+  // w_e <- w0_e phi(|R_j - R_i Rt_e|_F) on the device (mi_so3n_reweight; one read-back for the info).  The problem drops the
+  // model bound to any point, the speculative model and gradient of its trial chain and with them every point key: the
+  // class keeps none of its own (objective(), quadratic_model(), retraction() ... go to the problem handle each time), so a
+  // TNT / GradientDescent / TNLS call after this assembles at its start point with the new weights.  Operators handed out
+  // BEFORE (jacobian(), certificate_operator()) are to be requested again; gauss_newton_preconditioner() and
+  // preconditioner() stay valid.
+  ReweightInfo reweight(const Vector &R, const RobustKernel &k) {
+    double info[3];
+    check(mi_so3n_reweight(prob_, R.handle(), (int)k.kind, k.c, info));
+    ReweightInfo out;
+    out.robust_cost = info[0];
+    out.weighted_cost = info[1];
+    out.outliers = (size_t)info[2];
+    return out;
+  }
+  // back to the creation-time weights (no read-back)
+  void reset_weights() { check(mi_so3n_reweight(prob_, nullptr, MI_ROBUST_L2, 1.0, nullptr)); }
+  // the weights in force, the caller's edge order
+  std::vector<double> weights() const {
+    std::vector<double> w(E_);
+    check(mi_so3n_weights(prob_, w.data()));
+    return w;
   }
   // 3x3 block-Jacobi; valid after the first quadratic_model() call (TNT calls QM before precon)
   template <typename... Args>
