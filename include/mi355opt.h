@@ -558,6 +558,32 @@ MI_API int mi_so3n_cert_apply_blocks(mi_so3n_cert *cert, const struct mi_panel_b
 /* The 3N x 3 column-major panel Y (Y(3i + r, c) = R_i[c][r]) at the certificate's point: S Y = 0 at a critical point, so
  * these are the three eigenvectors at (or near) 0 -- the start block of an eigensolver deflates them.  Borrowed. */
 MI_API int mi_so3n_cert_null_panel(mi_so3n_cert *cert, mi_vec **Y);
+/* Spectral initialisation: a start point from the three lowest eigenvectors of the connection Laplacian Lap (above), each
+ * 3 x 3 block rounded to the nearest rotation.  Outside the method and NOT detected: a disconnected graph, weights <= 0.
+ * mi_so3n_laplacian: Lap as a handle of the certificate's type -- mi_so3n_cert_apply and mi_so3n_cert_apply_blocks work on
+ * it unchanged (the same kernel, the same bit contract); mi_so3n_cert_null_panel on it is MI_ERR_INVALID_ARGUMENT (it has no
+ * Y).  Owned by the problem in a slot of its own: mi_so3n_certificate does not rebind it, nor the other way round.  Every
+ * call refreshes the diagonal degw_i from the weights in force (after mi_so3n_reweight: the reweighted Laplacian), summed
+ * per node in slot order, no atomics, no sync.  Single-context only. */
+MI_API int mi_so3n_laplacian(mi_so3n *prob, mi_so3n_cert **out);
+/* Z = D^-1 X on column-major 3N x k panels (ld = 3N, 1 <= k <= 96), D = degw_i on the three rows of node i: the Jacobi
+ * preconditioner of Lap.  A node with degw_i = 0 copies.  The bits of X / degw; Z may be X; no sync.  Reads the diagonal of
+ * the latest mi_so3n_laplacian call (formed here on first use). */
+MI_API int mi_so3n_lap_jacobi(mi_so3n *prob, int k, const mi_vec *X, mi_vec *Z);
+/* R_i = the rotation nearest in the Frobenius norm to M_i = V[3i .. 3i+2, :]' of the column-major 3N x 3 panel V (the
+ * layout of mi_so3n_cert_null_panel), U diag(1, 1, det(U V')) V' for M_i = U Sigma V': a block with det < 0 has its smallest
+ * singular direction flipped.  Global sign first: when sum_i sign(det V_i) < 0 (an integer, counted on the device) -V is
+ * rounded instead -- a basis in the reflected gauge spans the same space; a tie does not flip.  A block with a non-finite
+ * entry, the zero block, or a block whose projection is not finite (rank one) becomes the identity and is counted as
+ * degenerate.  R: the 9N point (row-major blocks), not overlapping V.
+ * info (nullable) = {blocks with det V_i < 0 as given, flipped (0 / 1), degenerate blocks, min over the other blocks of
+ * (sigma_2 + d sigma_3) / sigma_1, d the sign of the determinant of the block that was rounded (NaN when every block is
+ * degenerate)}: one read-back (sync); info == NULL: no sync. */
+MI_API int mi_so3n_round(mi_so3n *prob, const mi_vec *V, mi_vec *R, double info[4]);
+/* The same projection block by block on a 9N point M (a user-supplied or drifted point with an orthogonality defect), no
+ * global sign; R may be M.  info (nullable) = {max over the non-degenerate blocks of |M_i' M_i - I|_F, degenerate blocks,
+ * blocks with det < 0}: one read-back (sync); info == NULL: no sync. */
+MI_API int mi_so3n_project(mi_so3n *prob, const mi_vec *M, mi_vec *R, double info[3]);
 /* Robust loss by iteratively reweighted least squares: the edge weights become w_e = w0_e phi(r_e) on the device, with
  * w0_e the creation-time weight, r_e = |R_j - R_i Rt_e|_F the UNWEIGHTED chordal residual at R, s = r_e^2 / c^2 and
  *   MI_ROBUST_L2             phi = 1                          rho = r^2 / 2

@@ -147,7 +147,9 @@ def build_harness(force=False):
       tests/cpp/libharness_certify_so3n.so MI355::RotationAveraging::certify: the certificate operator through LOBPCG,
                                       tagged and behind a plain lambda, after an optional TNT run
       tests/cpp/libharness_robust_so3n.so a GNC loop of TNT + MI355::RotationAveraging::reweight, every round repeated on a
-                                      fresh problem with the downloaded weights"""
+                                      fresh problem with the downloaded weights
+      tests/cpp/libharness_spectral_so3n.so MI355::RotationAveraging::spectral_initialization, then TNT from the spectral
+                                      point and certify at what it reaches"""
     tdir = os.path.join(ROOT, "tests", "cpp")
     inc = ["-I", os.path.join(HERE, "include"), "-I", os.path.join(ROOT, "oracle")]
     common = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-type-limits"]
@@ -192,7 +194,7 @@ def build_harness(force=False):
     # tests/cpp/harness_args.cpp, harness_lsqr_observer.cpp, harness_gd_so3n.cpp, harness_tnls_so3n.cpp: g++, and clang's front end on the same
     # translation units (the pack-carrying instantiations of the template layer must pass both)
     for name in ("harness_args", "harness_lsqr_observer", "harness_gd_so3n", "harness_tnls_so3n", "harness_certify_so3n",
-                 "harness_robust_so3n"):
+                 "harness_robust_so3n", "harness_spectral_so3n"):
         src = os.path.join(tdir, name + ".cpp")
         so = os.path.join(tdir, "lib" + name + ".so")
         if force or _newer(src, so, hdrs + [LIB]):

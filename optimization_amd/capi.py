@@ -209,6 +209,10 @@ def load():
         "mi_so3n_cert_apply": [vp, C.c_int, vp, vp],
         "mi_so3n_cert_apply_blocks": [vp, C.POINTER(PanelBlocks), vp],
         "mi_so3n_cert_null_panel": [vp, C.POINTER(vp)],
+        "mi_so3n_laplacian": [vp, C.POINTER(vp)],
+        "mi_so3n_lap_jacobi": [vp, C.c_int, vp, vp],
+        "mi_so3n_round": [vp, vp, vp, c_double_p],
+        "mi_so3n_project": [vp, vp, vp, c_double_p],
         "mi_so3n_reweight": [vp, vp, C.c_int, C.c_double, c_double_p],
         "mi_so3n_weights": [vp, c_double_p],
         "mi_stpcg_collect": [vp, C.POINTER(StpcgResult)],
@@ -1215,6 +1219,35 @@ class So3N:
         out = np.zeros(3)
         check(self.L.mi_so3n_certificate(self.h, R.h, C.byref(h), _dp(out)))
         return So3NCertificate(self, h), dict(f=out[0], stationarity=out[1], trace_C=out[2])
+
+    def laplacian(self):
+        """mi_so3n_laplacian: the connection Laplacian with the weights in force as a So3NCertificate (apply, apply_blocks;
+        no null_panel); problem-owned in a slot of its own, refreshed by every call"""
+        h = vp()
+        check(self.L.mi_so3n_laplacian(self.h, C.byref(h)))
+        return So3NCertificate(self, h)
+
+    def lap_jacobi(self, k, X, Z=None):
+        """mi_so3n_lap_jacobi: Z = X / degw row block by row block on column-major 3N x k panels (Z may be X)"""
+        Z = Z if Z is not None else Vec(self.ctx, 3 * self.N * k)
+        check(self.L.mi_so3n_lap_jacobi(self.h, k, X.h, Z.h))
+        return Z
+
+    def round(self, V, R=None, info=True):
+        """mi_so3n_round: (R Vec of 9N, dict(negative, flipped, degenerate, min_separation)) from the column-major 3N x 3
+        panel V; info=False: (R, None), no sync"""
+        R = R if R is not None else Vec(self.ctx, 9 * self.N)
+        out = np.zeros(4)
+        check(self.L.mi_so3n_round(self.h, V.h, R.h, _dp(out) if info else None))
+        return R, (dict(negative=int(out[0]), flipped=bool(out[1]), degenerate=int(out[2]), min_separation=out[3])
+                   if info else None)
+
+    def project(self, M, R=None, info=True):
+        """mi_so3n_project: (R Vec of 9N, dict(defect, degenerate, negative)) from the 9N point M; R may be M"""
+        R = R if R is not None else Vec(self.ctx, 9 * self.N)
+        out = np.zeros(3)
+        check(self.L.mi_so3n_project(self.h, M.h, R.h, _dp(out) if info else None))
+        return R, (dict(defect=out[0], degenerate=int(out[1]), negative=int(out[2])) if info else None)
 
     ROBUST = {"l2": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
 

@@ -40,6 +40,7 @@
 #include <algorithm>
 
 #include "mi_internal.h"
+#include "so3_round.h"
 
 using namespace mi;
 
@@ -884,6 +885,140 @@ __global__ __launch_bounds__(256) void k_so3_cert_panel(IncView inc, const doubl
   }
 }
 
+// ---- spectral initialisation and SO(3) rounding ----------------------------------------------------------
+// The connection Laplacian is the certificate matrix with the diagonal blocks degw_i I: k_so3_cert_panel is its panel
+// product once Esl holds them.  k_so3_lap_diag: one lane per node on the walk of k_so3_cert_diag, degw_i summed from winc in
+// slot order (the weights IN FORCE: after mi_so3n_reweight the reweighted Laplacian; weight-0 slots skipped as there), the
+// six entries (degw, 0, 0, degw, 0, degw) into the layout of k_so3_cert_diag; padding lanes write 0.  No atomics.
+// Algorithmic bytes: 8 padded + 48 * 64 nslices + 4 N
+__global__ __launch_bounds__(256) void k_so3_lap_diag(IncView inc, const double *__restrict__ winc, double *__restrict__ Esl) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const size_t ngroups = (inc.nslices + 3) / 4;
+  for (size_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const size_t slice = grp * 4 + w;
+    if (slice >= inc.nslices) continue;
+    const bool live = inc.perm[slice * 64 + lane] >= 0;
+    double degw = 0;
+    const long long b0 = inc.slice_ptr[slice], b1 = inc.slice_ptr[slice + 1];
+    for (long long k = b0; k < b1; ++k) {
+      const double we = winc[(size_t)k * 64 + lane];
+      if (live && we != 0) degw += we;
+    }
+    double *Es = Esl + slice * 6 * 64 + lane;
+    Es[0] = degw; Es[64] = 0.0; Es[128] = 0.0;
+    Es[192] = degw; Es[256] = 0.0; Es[320] = degw;
+  }
+}
+// Z = D^-1 X on column-major 3N x k panels (ld = 3N), D = degw_i on the three rows of node i, read from the Laplacian's
+// diagonal (entry 0 of Esl, slice order): the Jacobi preconditioner of the spectral solve.  A node with degw_i = 0 copies.
+// One lane per node; a true division (the bits of X / degw).  Z may be X.
+__global__ __launch_bounds__(256) void k_so3_lap_jacobi(IncView inc, const double *__restrict__ Esl, int k, const double *X,
+                                                        double *Z) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const size_t ngroups = (inc.nslices + 3) / 4, ld = 3 * inc.N;
+  for (size_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const size_t slice = grp * 4 + w;
+    if (slice >= inc.nslices) continue;
+    const int node = inc.perm[slice * 64 + lane];
+    if (node < 0) continue;
+    const double degw = Esl[slice * 6 * 64 + lane];
+    const bool scale = degw != 0;
+    const size_t r0 = 3 * (size_t)node;
+    for (int c = 0; c < k; ++c) {
+      const double *x = X + (size_t)c * ld + r0;
+      double *z = Z + (size_t)c * ld + r0;
+      const double x0 = x[0], x1 = x[1], x2 = x[2];
+      z[0] = scale ? x0 / degw : x0; z[1] = scale ? x1 / degw : x1; z[2] = scale ? x2 / degw : x2;
+    }
+  }
+}
+
+// The four 8-byte words one rounding call leaves on the device (mi_so3n::round_words; all integer adds and order-preserving
+// integer min / max: the same bits on every run):
+//   [0] sum_i sign(det V_i) as a two's-complement integer (k_so3_round_sign; the panel form only)
+//   [1] blocks with det < 0 as given   [2] degenerate blocks
+//   [3] the bits of a double >= 0: min over the other blocks of (sigma_2 + d sigma_3) / sigma_1 (panel form) or max of
+//       |M_i' M_i - I|_F (point form) -- the bit pattern of a non-negative double orders as the number does
+enum { RW_SIGN = 0, RW_NEG = 1, RW_DEGENERATE = 2, RW_EXTREME = 3, RW_WORDS = 4 };
+__global__ void k_so3_round_init(unsigned long long *words, unsigned long long extreme) {
+  words[RW_SIGN] = 0; words[RW_NEG] = 0; words[RW_DEGENERATE] = 0; words[RW_EXTREME] = extreme;
+}
+// block i of the column-major 3N x 3 panel as M_i = V[3i .. 3i+2, :]' (the layout of Yp in k_so3_cert_diag), row-major
+__device__ __forceinline__ void load_panel_block(const double *__restrict__ V, size_t ld, size_t i, double *M) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) M[3 * r + c] = V[(size_t)r * ld + 3 * i + c];
+}
+// the counting pass of the global sign: sum_i sign(det V_i) (0 for det = 0 or NaN) into words[RW_SIGN]
+__global__ __launch_bounds__(256) void k_so3_round_sign(size_t N, const double *__restrict__ V, unsigned long long *words) {
+  const size_t stride = (size_t)gridDim.x * 256, ld = 3 * N;
+  double acc = 0;  // (an integer of magnitude <= N < 2^31: exact)
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N; i += stride) {
+    double M[9];
+    load_panel_block(V, ld, i, M);
+    const double det = so3_det3(M);
+    acc += det > 0 ? 1.0 : det < 0 ? -1.0 : 0.0;
+  }
+  acc = wave_reduce_sum(acc);
+  if ((threadIdx.x & 63) == 0 && acc != 0) atomicAdd(words + RW_SIGN, (unsigned long long)(long long)acc);
+}
+// R_i = the rotation nearest to M_i (so3_round.h), one lane per node, everything in registers.
+// PANEL: M_i from the eigenvector panel, negated when the sign sum of k_so3_round_sign is negative (a basis that landed in
+// the reflected gauge: -V spans the same space; a tie does not flip); else M_i = row-major block i of the 9N point, and
+// the orthogonality defect of the input rides along.  in may be out in the point form (a lane reads its block first).
+template <bool PANEL>
+__global__ __launch_bounds__(256) void k_so3_round(size_t N, const double *in, double *out, unsigned long long *words) {
+  const size_t stride = (size_t)gridDim.x * 256, ld = 3 * N;
+  const bool flip = PANEL && (long long)words[RW_SIGN] < 0;
+  double neg = 0, deg = 0, ext = PANEL ? HUGE_VAL : 0.0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N; i += stride) {
+    double M[9], Ri[9], sep, d;
+    bool degenerate;
+    if (PANEL) {
+      load_panel_block(in, ld, i, M);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 9; ++c) M[c] = in[9 * i + c];
+    }
+    neg += so3_det3(M) < 0 ? 1.0 : 0.0;
+    if (flip) {
+#pragma unroll
+      for (int c = 0; c < 9; ++c) M[c] = -M[c];
+    }
+    so3_nearest_rotation(M, Ri, sep, d, degenerate);
+    deg += degenerate ? 1.0 : 0.0;
+    if (PANEL) {
+      if (!degenerate) ext = fmin(ext, sep);
+    } else {
+      double G[9], q = 0;
+      mat3_mul_at(M, M, G);
+#pragma unroll
+      for (int c = 0; c < 9; ++c) {
+        const double e = G[c] - (c % 4 == 0 ? 1.0 : 0.0);
+        q += e * e;
+      }
+      if (!degenerate && q == q) ext = fmax(ext, sqrt(q));
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) out[9 * i + c] = Ri[c];
+  }
+  neg = wave_reduce_sum(neg);
+  deg = wave_reduce_sum(deg);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_down(ext, off, 64);
+    ext = PANEL ? fmin(ext, o) : fmax(ext, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (neg != 0) atomicAdd(words + RW_NEG, (unsigned long long)neg);
+    if (deg != 0) atomicAdd(words + RW_DEGENERATE, (unsigned long long)deg);
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(ext);
+    if (PANEL) atomicMin(words + RW_EXTREME, bits);
+    else atomicMax(words + RW_EXTREME, bits);
+  }
+}
+
 int upload(void **dst, const void *src, size_t bytes) {
   MI_HIP(hipMalloc(dst, bytes ? bytes : 8));
   if (bytes) MI_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
@@ -945,6 +1080,8 @@ struct mi_so3n {
   mi_vec *gn_diag = nullptr;        // 3N: 1 / sqrt(2 degw_i), each three times
   mi_op *gn_op = nullptr;
   mi_so3n_cert *cert = nullptr;     // mi_so3n_certificate: owned here, rebound by every call
+  mi_so3n_cert *lap = nullptr;      // mi_so3n_laplacian: a slot of its own (Y stays null), refreshed by every call
+  unsigned long long *round_words = nullptr;  // device, RW_WORDS: what mi_so3n_round / mi_so3n_project count
   // ---- mi_so3n_reweight: device, E each, from the first reweighting on.  w_cur != nullptr <=> the weights in force are
   // w_cur (what winc, swe and gn_diag were last written from), not h_w: every later first-use path reads it
   double *w0 = nullptr, *w_cur = nullptr;
@@ -1250,6 +1387,11 @@ int mi_so3n_destroy(mi_so3n *q) {
     mi_vec_destroy(q->cert->Y);
     delete q->cert;
   }
+  if (q->lap) {
+    (void)hipFree(q->lap->Esl);
+    delete q->lap;
+  }
+  (void)hipFree(q->round_words);
   delete q;
   return MI_OK;
 }
@@ -1794,7 +1936,123 @@ int mi_so3n_cert_apply_blocks(mi_so3n_cert *c, const mi_panel_blocks *X, mi_vec 
 
 int mi_so3n_cert_null_panel(mi_so3n_cert *c, mi_vec **Y) {
   SO3_REQUIRE_ARGS(c && Y);
+  MI_REQUIRE(c->Y, "the connection Laplacian of mi_so3n_laplacian has no panel Y");
   *Y = c->Y;
+  return MI_OK;
+}
+
+}  // extern "C"
+
+// ---- spectral initialisation (kernels: k_so3_lap_diag, k_so3_lap_jacobi, k_so3_round_sign, k_so3_round) ----
+namespace {
+
+// the Laplacian's handle, its diagonal written from the weights in force
+int lap_refresh(mi_so3n *q) {
+  mi_ctx *ctx = q->ctx;
+  MI_REQUIRE(!ctx->uniform_grid, "the connection Laplacian of mi_so3n is single-context");
+  if (!q->lap) {
+    mi_so3n_cert *c = new mi_so3n_cert();
+    c->q = q;
+    q->lap = c;
+    MI_HIP(hipMalloc((void **)&c->Esl, q->nslices * 6 * 64 * sizeof(double)));
+  }
+  hipLaunchKernelGGL(k_so3_lap_diag, dim3(node_grid(q)), dim3(256), 0, ctx->stream, view(q), (const double *)q->winc,
+                     q->lap->Esl);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+// the count words of one rounding call, zeroed (RW_EXTREME: the neutral element of the call's min or max)
+int round_words_init(mi_so3n *q, double extreme) {
+  if (!q->round_words) MI_HIP(hipMalloc((void **)&q->round_words, RW_WORDS * sizeof(unsigned long long)));
+  unsigned long long bits;
+  std::memcpy(&bits, &extreme, sizeof(bits));
+  hipLaunchKernelGGL(k_so3_round_init, dim3(1), dim3(1), 0, q->ctx->stream, q->round_words, bits);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+int round_words_read(mi_so3n *q, const char *what, unsigned long long words[RW_WORDS]) {
+  MI_TRY(stream_wait(q->ctx, what));
+  MI_HIP(hipMemcpy(words, q->round_words, RW_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+double word_as_double(unsigned long long w) {
+  double d;
+  std::memcpy(&d, &w, sizeof(d));
+  return d;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_so3n_laplacian(mi_so3n *q, mi_so3n_cert **out) {
+  SO3_REQUIRE_ARGS(q && out);
+  MI_TRY(lap_refresh(q));
+  *out = q->lap;
+  return MI_OK;
+}
+
+int mi_so3n_lap_jacobi(mi_so3n *q, int k, const mi_vec *X, mi_vec *Z) {
+  SO3_REQUIRE_ARGS(q && X && Z);
+  MI_REQUIRE(k >= 1 && k <= kCertMaxK, "panel width must be in [1,%d]", kCertMaxK);
+  const size_t m = 3 * q->N;
+  MI_REQUIRE(X->ctx == q->ctx && Z->ctx == q->ctx, "panel belongs to another context");
+  MI_REQUIRE(X->n >= m * (size_t)k, "X holds %zu doubles, needs 3N * k = %zu * %d", X->n, m, k);
+  MI_REQUIRE(Z->n >= m * (size_t)k, "Z holds %zu doubles, needs 3N * k = %zu * %d", Z->n, m, k);
+  MI_REQUIRE(Z->d == X->d || Z->d + m * (size_t)k <= X->d || X->d + m * (size_t)k <= Z->d,
+             "input and output panels must be the same or not overlap");
+  if (!q->lap) MI_TRY(lap_refresh(q));  // (else: the diagonal of the latest mi_so3n_laplacian call)
+  touch(Z);
+  hipLaunchKernelGGL(k_so3_lap_jacobi, dim3(node_grid(q)), dim3(256), 0, q->ctx->stream, view(q), (const double *)q->lap->Esl,
+                     k, (const double *)X->d, Z->d);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+int mi_so3n_round(mi_so3n *q, const mi_vec *V, mi_vec *R, double info[4]) {
+  SO3_REQUIRE_ARGS(q && V && R);
+  const size_t n9 = 9 * q->N;
+  MI_REQUIRE(V->ctx == q->ctx && V->n >= n9, "V must hold the column-major 3N x 3 panel");
+  MI_REQUIRE(R->ctx == q->ctx && R->n == n9, "R must hold N row-major 3x3 blocks");
+  MI_REQUIRE(R->d + n9 <= V->d || V->d + n9 <= R->d, "the panel and the point must not overlap");
+  mi_ctx *ctx = q->ctx;
+  MI_TRY(round_words_init(q, HUGE_VAL));
+  touch(R);
+  const int grid = grid_for(ctx, q->N, 1);
+  hipLaunchKernelGGL(k_so3_round_sign, dim3(grid), dim3(256), 0, ctx->stream, q->N, (const double *)V->d, q->round_words);
+  hipLaunchKernelGGL(k_so3_round<true>, dim3(grid), dim3(256), 0, ctx->stream, q->N, (const double *)V->d, R->d,
+                     q->round_words);
+  MI_HIP(hipGetLastError());
+  if (info) {
+    unsigned long long w[RW_WORDS];
+    MI_TRY(round_words_read(q, "mi_so3n_round", w));  // the one read-back
+    info[0] = (double)w[RW_NEG];
+    info[1] = (long long)w[RW_SIGN] < 0 ? 1.0 : 0.0;
+    info[2] = (double)w[RW_DEGENERATE];
+    info[3] = w[RW_DEGENERATE] == q->N ? std::nan("") : word_as_double(w[RW_EXTREME]);
+  }
+  return MI_OK;
+}
+
+int mi_so3n_project(mi_so3n *q, const mi_vec *M, mi_vec *R, double info[3]) {
+  SO3_REQUIRE_ARGS(q && M && R);
+  const size_t n9 = 9 * q->N;
+  MI_REQUIRE(M->ctx == q->ctx && M->n == n9, "M must hold N row-major 3x3 blocks");
+  MI_REQUIRE(R->ctx == q->ctx && R->n == n9, "R must hold N row-major 3x3 blocks");
+  MI_REQUIRE(R->d == M->d || R->d + n9 <= M->d || M->d + n9 <= R->d, "R must be M itself or not overlap it");
+  mi_ctx *ctx = q->ctx;
+  MI_TRY(round_words_init(q, 0.0));
+  touch(R);
+  hipLaunchKernelGGL(k_so3_round<false>, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, (const double *)M->d,
+                     R->d, q->round_words);
+  MI_HIP(hipGetLastError());
+  if (info) {
+    unsigned long long w[RW_WORDS];
+    MI_TRY(round_words_read(q, "mi_so3n_project", w));  // the one read-back
+    info[0] = word_as_double(w[RW_EXTREME]);
+    info[1] = (double)w[RW_DEGENERATE];
+    info[2] = (double)w[RW_NEG];
+  }
   return MI_OK;
 }
 

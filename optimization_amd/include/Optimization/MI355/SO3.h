@@ -8,6 +8,8 @@
 // The same problem as a nonlinear least-squares one, f = 1/2 |F(R)|^2 with F_e = sqrt(w_e) (R_j - R_i Rt_e) in R^{9E}:
 // residual(), jacobian(), residual_inner_product() and gauss_newton_preconditioner() are the arguments of
 // Riemannian::TNLS (with metric() and retraction() from above); every inner solve then runs in the fused mi_lsqr.
+// A start point: spectral_initialization() rounds the three lowest eigenvectors of the connection Laplacian
+// (laplacian_operator(), LOBPCG) to SO(3)^N; project() takes a point with an orthogonality defect back onto it.
 // Global optimality: certificate_operator(R) is the certificate matrix S(R) of mi_so3n_certificate as a
 // SymmetricLinearOperator on device panels, certify(R) its smallest eigenvalue through LinearAlgebra::LOBPCG and the
 // verdict that follows from it.
@@ -72,6 +74,63 @@ struct CertifyResult {
   double eta = 0;              // the threshold used
   size_t iterations = 0;
   bool converged = false, certified = false;
+};
+
+// The connection Laplacian (mi355opt.h: mi_so3n_laplacian) as a callable on column-major 3N x k device panels, tagged as
+// CertificateOperator is.  The handle is the problem's, in a slot of its own; its diagonal is that of the latest
+// laplacian_operator() / spectral_initialization() call (the weights then in force).
+struct LaplacianOperator {
+  mi_so3n_cert *lap = nullptr;
+  const void *owner = nullptr;
+  size_t N = 0;
+  DeviceMatrix operator()(const DeviceMatrix &X) const {
+    DeviceMatrix Z(X.context(), X.rows(), X.cols());
+    check(mi_so3n_cert_apply(lap, (int)X.cols(), X.handle(), Z.handle()));
+    return Z;
+  }
+  DeviceMatrix operator()(const PanelBlocks &X) const {
+    DeviceMatrix Z(X.context(), X.rows(), X.cols());
+    const mi_panel_blocks b = X.raw();
+    check(mi_so3n_cert_apply_blocks(lap, &b, Z.handle()));
+    return Z;
+  }
+};
+// Z = D^-1 X, D = degw_i on the rows of node i (mi_so3n_lap_jacobi): LOBPCG's T for the Laplacian
+struct LaplacianJacobi {
+  mi_so3n *prob = nullptr;
+  const void *owner = nullptr;
+  DeviceMatrix operator()(const DeviceMatrix &X) const {
+    DeviceMatrix Z(X.context(), X.rows(), X.cols());
+    check(mi_so3n_lap_jacobi(prob, (int)X.cols(), X.handle(), Z.handle()));
+    return Z;
+  }
+};
+
+struct RoundInfo {
+  size_t negative = 0;       // blocks with det < 0 as given
+  bool flipped = false;      // the panel was rounded as -V (round only)
+  size_t degenerate = 0;     // blocks replaced by the identity
+  double min_separation = 0; // round: min (sigma_2 + d sigma_3) / sigma_1 over the other blocks
+  double defect = 0;         // project: max |M_i' M_i - I|_F over the other blocks
+};
+struct SpectralParams {
+  size_t nx = 6;             // block size of the eigensolver (at least 3)
+  double tau = 1e-6;         // LOBPCG's relative residual tolerance
+  size_t max_iterations = 1000;
+  bool precondition = true;  // T = the Laplacian's Jacobi scaling
+};
+struct SpectralResult {
+  DeviceVector R;                      // the rounded point, 9N
+  DeviceMatrix eigenvectors;           // 3N x 3: what was rounded (empty when no solve was needed)
+  double eigenvalues[3] = {0, 0, 0};   // the three lowest Ritz values of the Laplacian
+  double f = 0;                        // f(R)
+  double lower_bound = 0;              // (N / 2) sum_i (theta_i - |r_i| / |x_i|) <= min f when every measurement is a rotation
+                                       // (NaN otherwise), PROVIDED the theta_i track the three smallest eigenvalues (LOBPCG
+                                       // converges to them from a generic start block; it is not proved to: see certify)
+  size_t iterations = 0;
+  bool converged = false, flipped = false;
+  size_t degenerate = 0;
+  double min_separation = 0;
 };
 
 // A robust loss for RotationAveraging::reweight (mi355opt.h: mi_so3n_reweight): the weight function phi(r; c) applied to
@@ -278,6 +337,108 @@ class RotationAveraging {
     out.iterations = iters;
     out.converged = nc == nev;
     out.certified = out.converged && out.lambda_min_safe >= -out.eta;
+    return out;
+  }
+  // --- spectral initialisation -------------------------------------------------------------------------------------
+  // A start point without one: the three lowest eigenvectors of the connection Laplacian, each 3 x 3 block rounded to the
+  // nearest rotation.  Outside the method and NOT detected: a disconnected graph (more than three eigenvalues at 0: the
+  // blocks of different components come out in unrelated gauges) and weights <= 0.
+  // The Laplacian with the weights in force as LOBPCG's operator A (a LaplacianOperator inside)
+  LinearAlgebra::SymmetricLinearOperator<DeviceMatrix> laplacian_operator() {
+    LaplacianOperator op;
+    op.owner = this;
+    op.N = N_;
+    check(mi_so3n_laplacian(prob_, &op.lap));
+    return op;
+  }
+  // its Jacobi scaling as LOBPCG's T (reads the diagonal of the latest laplacian_operator() call)
+  LinearAlgebra::SymmetricLinearOperator<DeviceMatrix> laplacian_preconditioner() { return LaplacianJacobi{prob_, this}; }
+  // the 3N x 3 panel V block by block to SO(3), after the global sign (mi_so3n_round); info: one read-back, else none
+  Vector round(const DeviceMatrix &V, RoundInfo *info = nullptr) {
+    Vector R(ctx_, 9 * N_);
+    double buf[4];
+    check(mi_so3n_round(prob_, V.handle(), R.handle(), info ? buf : nullptr));
+    if (info) {
+      info->negative = (size_t)buf[0];
+      info->flipped = buf[1] != 0;
+      info->degenerate = (size_t)buf[2];
+      info->min_separation = buf[3];
+    }
+    return R;
+  }
+  // a 9N point with an orthogonality defect back onto SO(3)^N (mi_so3n_project)
+  Vector project(const Vector &M, RoundInfo *info = nullptr) {
+    Vector R(ctx_, 9 * N_);
+    double buf[3];
+    check(mi_so3n_project(prob_, M.handle(), R.handle(), info ? buf : nullptr));
+    if (info) {
+      info->defect = buf[0];
+      info->degenerate = (size_t)buf[1];
+      info->negative = (size_t)buf[2];
+    }
+    return R;
+  }
+  // LOBPCG (nev = 3) on the Laplacian from the default-seeded gaussian_probe block, then round.  A problem of at most
+  // kSpectralDenseRows = 96 rows (N <= 32: one panel of the widest product) is solved densely on the host instead
+  // (iterations = 0).  E == 0 returns identities without a solve.
+  static constexpr size_t kSpectralDenseRows = 96;
+  SpectralResult spectral_initialization(const SpectralParams &params = SpectralParams()) {
+    using Op = LinearAlgebra::SymmetricLinearOperator<DeviceMatrix>;
+    SpectralResult out;
+    const size_t m = 3 * N_, nev = 3;
+    if (E_ == 0) {
+      std::vector<double> eye(9 * N_, 0.0);
+      for (size_t i = 0; i < N_; ++i) eye[9 * i] = eye[9 * i + 4] = eye[9 * i + 8] = 1.0;
+      out.R = Vector(ctx_, eye);
+      out.converged = true;
+      out.min_separation = 2;
+      return out;
+    }
+    const Op A = laplacian_operator();
+    const size_t nx = std::max(nev, params.nx);
+    HostVectorD theta;
+    DeviceMatrix V;
+    if (m <= kSpectralDenseRows) {
+      // the Laplacian read off the device operator (Lap I) and solved on the host: exact, and LOBPCG's basis of 3 nx
+      // columns is not asked to stay independent in a space that is hardly larger
+      std::vector<double> eye(m * m, 0.0);
+      for (size_t i = 0; i < m; ++i) eye[i + i * m] = 1.0;
+      const std::vector<double> lap = A(DeviceMatrix(ctx_, m, m, eye.data())).to_host();
+      HostMatrix Lh(m, m), Ih(m, m);
+      std::copy(lap.begin(), lap.end(), Lh.data());
+      std::copy(eye.begin(), eye.end(), Ih.data());
+      auto tc = rayleigh_ritz(Lh, Ih);
+      theta = tc.first.head(nev);
+      V = DeviceMatrix(ctx_, m, nev, tc.second.data());
+      out.converged = true;
+    } else {
+      const DeviceMatrix X0 = gaussian_probe(DeviceMatrix(ctx_, 1, 1), m, nx);
+      const std::optional<Op> T = params.precondition ? std::optional<Op>(laplacian_preconditioner()) : std::optional<Op>();
+      size_t iters = 0, nc = 0;
+      auto tx = LinearAlgebra::LOBPCG<HostVectorD, DeviceMatrix, double>(A, std::optional<Op>(), T, X0, nev,
+                                                                         params.max_iterations, iters, nc, params.tau);
+      theta = tx.first;
+      V = std::move(tx.second);
+      out.iterations = iters;
+      out.converged = nc == nev;
+    }
+    HostVectorD r, xn;
+    (void)residual_and_norms(A(V), V, V, theta, r, xn);
+    size_t forms[6];
+    check(mi_debug_so3n_info(prob_, forms));
+    double safe = 0;
+    for (size_t i = 0; i < nev; ++i) {
+      out.eigenvalues[i] = theta(i);
+      safe += theta(i) - r(i) / xn(i);
+    }
+    out.lower_bound = forms[0] ? .5 * (double)N_ * safe : std::nan("");
+    RoundInfo info;
+    out.R = round(V, &info);
+    out.flipped = info.flipped;
+    out.degenerate = info.degenerate;
+    out.min_separation = info.min_separation;
+    check(mi_so3n_objective(prob_, out.R.handle(), &out.f));
+    out.eigenvectors = std::move(V);
     return out;
   }
   // --- robust loss -------------------------------------------------------------------------------------------------
