@@ -288,10 +288,14 @@ def _sanitizer_probe(tdir, san):
         raise SanitizerUnavailable("a trivial sanitized program does not run here:\n" + r.stderr[-800:])
 
 
+_SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1", "-ffp-contract=off"]
+
+
 def build_sanitize(force=False, run=True):
     """tests/cpp/sanitize_host: the template layer on a host vector (the host harness's translation unit + a main that
     drives TNT, GradientDescent, LSQR, TNLS, LOBPCG once) under -fsanitize=address,undefined; run here, any REPORT is a
-    build failure (the sanitizer / host-hardening target).  A host without the sanitizer runtime raises
+    build failure (the sanitizer / host-hardening target); beside it tests/cpp/sanitize_so3_pack, the
+    host-side layout of csrc/so3_pack.h with its failure paths.  A host without the sanitizer runtime raises
     SanitizerUnavailable, which __graft_entry__.build() turns into a warning."""
     tdir = os.path.join(ROOT, "tests", "cpp")
     odir = os.path.join(ROOT, "oracle")
@@ -299,8 +303,7 @@ def build_sanitize(force=False, run=True):
     src = os.path.join(tdir, "sanitize_host.cpp")
     deps = glob.glob(os.path.join(HERE, "include", "Optimization", "*", "*.h")) + glob.glob(os.path.join(odir, "*.inc")) + \
         glob.glob(os.path.join(odir, "*.[ch]")) + [os.path.join(tdir, "harness_host.cpp")]
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1",
-           "-ffp-contract=off"]
+    san = _SAN
     asan_opts = _sanitizer_probe(tdir, san)
     if force or _newer(src, exe, deps):
         objs = []
@@ -321,6 +324,27 @@ def build_sanitize(force=False, run=True):
                            env=dict(os.environ, ASAN_OPTIONS=asan_opts, UBSAN_OPTIONS="print_stacktrace=1"))
         if r.returncode != 0 or "sanitize_host: ok" not in r.stdout:
             raise RuntimeError("the template layer failed under ASan/UBSan:\n" + r.stdout[-2000:] + r.stderr[-6000:])
+    # (a tree that carries another version of tests/ may not have the packer's program: it has no test of it either)
+    if os.path.exists(os.path.join(tdir, "sanitize_so3_pack.cpp")):
+        build_sanitize_so3_pack(force=force, run=run)
+    return exe
+
+
+def build_sanitize_so3_pack(force=False, run=True):
+    """tests/cpp/sanitize_so3_pack: the host-side layout of an SO(3)^N problem (csrc/so3_pack.h) with its failure paths,
+    on its own under the same sanitizers; built and run by build_sanitize() and by tests/test_cpu_so3n_pack.py."""
+    tdir = os.path.join(ROOT, "tests", "cpp")
+    exe, src = os.path.join(tdir, "sanitize_so3_pack"), os.path.join(tdir, "sanitize_so3_pack.cpp")
+    asan_opts = _sanitizer_probe(tdir, _SAN)
+    if force or _newer(src, exe, [os.path.join(CSRC, "so3_pack.h")]):
+        r = subprocess.run(["g++", "-std=c++17", "-Wall"] + _SAN + ["-I", CSRC, src, "-o", exe], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("sanitizer build failed:\n" + r.stderr[-6000:])
+    if run:
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=600,
+                           env=dict(os.environ, ASAN_OPTIONS=asan_opts, UBSAN_OPTIONS="print_stacktrace=1"))
+        if r.returncode != 0 or "sanitize_so3_pack: ok" not in r.stdout:
+            raise RuntimeError("so3_pack.h failed under ASan/UBSan:\n" + r.stdout[-2000:] + r.stderr[-6000:])
     return exe
 
 

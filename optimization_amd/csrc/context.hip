@@ -160,6 +160,18 @@ void pool_free(mi_ctx *ctx, void *p) {
   ctx->pool_free.insert({it->second, p});
 }
 
+int upload(void **dst, const void *src, size_t bytes) {
+  void *p = nullptr;
+  MI_HIP(hipMalloc(&p, bytes ? bytes : 8));
+  const hipError_t e = bytes ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+  if (e != hipSuccess) {
+    (void)hipFree(p);
+    return hip_fail(e, "hipMemcpy(p, src, bytes, hipMemcpyHostToDevice)", __FILE__, __LINE__);
+  }
+  *dst = p;
+  return MI_OK;
+}
+
 int stage_upload(mi_ctx *ctx, const void *src, size_t bytes, void *dst_dev) {
   MI_REQUIRE(bytes <= mi_ctx::kStageBytes, "staged upload of %zu bytes exceeds the slot size", bytes);
   const int slot = ctx->stage_next;

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <set>
 #include <vector>
@@ -326,6 +327,10 @@ namespace mi {
 
 int pool_alloc(mi_ctx *ctx, size_t bytes, void **out);
 void pool_free(mi_ctx *ctx, void *p);
+// a device allocation of its own (hipMalloc, at least 8 bytes) holding a copy of `bytes` of host memory; blocking
+// (context.hip).  *dst stays null when either step fails.
+int upload(void **dst, const void *src, size_t bytes);
+
 // Asynchronous upload of <= mi_ctx::kStageBytes from pageable host memory: copied into a pinned slot of a small ring
 // and from there in-stream; the caller's buffer may die at once, the host does not wait for the device (a slot is
 // reused only after the copy that read it has completed).
@@ -768,3 +773,49 @@ struct mi_precon {
   // mi_stpcg copies it behind the solve's own state read-back and answers MI_ERR_INTERNAL if it is set.
   double *fail_word = nullptr;
 };
+
+namespace mi {
+
+// Owners for the members of a problem object, so that its destructor -- and every early return on the way to a complete
+// one -- releases what was made so far.  Move-only; get(), std::swap and `if (p)` as std::unique_ptr has them.
+//   DevPtr<T>        a hipMalloc allocation of T (hipFree)
+//   Owned<mi_vec>, Owned<mi_op>, Owned<mi_so3n_cert>   a handle (its destroy function; an operator the problem lends out
+//                    as `borrowed` is the owner's to destroy)
+struct DevFree {
+  void operator()(void *p) const { (void)hipFree(p); }
+};
+template <class T>
+using DevPtr = std::unique_ptr<T, DevFree>;
+struct HandleDestroy {
+  void operator()(mi_vec *v) const { (void)mi_vec_destroy(v); }
+  void operator()(mi_op *o) const {
+    o->borrowed = false;
+    (void)mi_op_destroy(o);
+  }
+  void operator()(mi_so3n_cert *c) const;  // so3.hip
+};
+template <class T>
+using Owned = std::unique_ptr<T, HandleDestroy>;
+// p <- a fresh allocation of `count` elements, uninitialised / copied from the host (blocking); p is left as it was on failure
+template <class T>
+int dev_alloc(DevPtr<T> &p, size_t count) {
+  void *raw = nullptr;
+  MI_HIP(hipMalloc(&raw, count ? count * sizeof(T) : 8));
+  p.reset((T *)raw);
+  return MI_OK;
+}
+inline int vec_alloc(mi_ctx *ctx, size_t n, Owned<mi_vec> &out) {  // (a vector of the context's pool)
+  mi_vec *v = nullptr;
+  MI_TRY(mi_vec_create(ctx, n, &v));
+  out.reset(v);
+  return MI_OK;
+}
+template <class T>
+int dev_upload(DevPtr<T> &p, const T *src, size_t count) {
+  void *raw = nullptr;
+  MI_TRY(upload(&raw, src, count * sizeof(T)));
+  p.reset((T *)raw);
+  return MI_OK;
+}
+
+}  // namespace mi

@@ -40,6 +40,7 @@
 #include <algorithm>
 
 #include "mi_internal.h"
+#include "so3_pack.h"
 #include "so3_round.h"
 
 using namespace mi;
@@ -183,17 +184,6 @@ __device__ __forceinline__ void so3_model_slice(const IncView &inc, const double
     if (live && we != 0) {
       const size_t j = (size_t)inc.nbr[e0];
       double S[9], Rj[9];
-#if defined(MI_SO3_ABLATE_GATHER4)  // (timing experiment only: a 32-byte record per neighbour -- wrong results)
-      {
-        const double2 q0 = *reinterpret_cast<const double2 *>(R + 8 * (j & ~(size_t)1)), q1 = *reinterpret_cast<const double2 *>(R + 8 * (j & ~(size_t)1) + 2);
-        Rj[0] = q0.x; Rj[1] = q0.y; Rj[2] = q1.x; Rj[3] = q1.y;
-#pragma unroll
-        for (int c = 4; c < 9; ++c) Rj[c] = Rj[c - 4] + 1.0;
-      }
-#elif defined(MI_SO3_ABLATE_GATHER0)  // (no neighbour gather at all)
-#pragma unroll
-      for (int c = 0; c < 9; ++c) Rj[c] = Ri[c] + we;
-#else
       if (GQ) {
         const double2 qa = *reinterpret_cast<const double2 *>(Rq + 4 * j), qb = *reinterpret_cast<const double2 *>(Rq + 4 * j + 2);
         quat_to_mat(qa.x, qa.y, qb.x, qb.y, Rj);
@@ -201,7 +191,6 @@ __device__ __forceinline__ void so3_model_slice(const IncView &inc, const double
 #pragma unroll
         for (int c = 0; c < 9; ++c) Rj[c] = R[9 * j + c];
       }
-#endif
       // head: term R_i - R_j Rt (j = tail); tail: R_i - R_j Rt'  (the transposition is in Sinc)
       if (SQ) {
         const double *sq = Sinc + (size_t)k * 4 * 64 + lane;
@@ -300,7 +289,7 @@ __global__ __launch_bounds__(256) void k_so3_model(IncView inc, const double *__
   }
 }
 // The gradient-only form: grid, workgroup shape and objective partial rows of k_so3_model (see there), so that
-// model_objective_to_slot reduces f exactly as mi_so3n_objective does; the gradient bit for bit the one
+// partial_rows_to_slot reduces f exactly as mi_so3n_objective does; the gradient bit for bit the one
 // k_so3_model<true> writes.  (A kernel of its own, not a third value of MODEL: the existing instantiations keep their
 // names and their code.  The lines around the slice walk are repeated here on purpose: as one inlined function shared with
 // k_so3_model they compile to other register counts in the 9-component-measurement forms -- k_so3_model<true, false,
@@ -1019,95 +1008,98 @@ __global__ __launch_bounds__(256) void k_so3_round(size_t N, const double *in, d
   }
 }
 
-int upload(void **dst, const void *src, size_t bytes) {
-  MI_HIP(hipMalloc(dst, bytes ? bytes : 8));
-  if (bytes) MI_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return MI_OK;
-}
-
 }  // namespace
 
 // The certificate matrix S(R) of mi_so3n_certificate: the problem's static incidence streams plus a copy of what depends
 // on the point (the diagonal blocks E_i = degw_i I - C_i, the panel Y), written by k_so3_cert_diag and by nothing else
 struct mi_so3n_cert {
   mi_so3n *q = nullptr;
-  double *Esl = nullptr;  // nslices * 6 * 64: the six distinct entries of E_i in slice order
-  mi_vec *Y = nullptr;    // 9N: the column-major 3N x 3 panel Y, Y_i = R_i'
+  DevPtr<double> Esl;  // nslices * 6 * 64: the six distinct entries of E_i in slice order
+  Owned<mi_vec> Y;     // 9N: the column-major 3N x 3 panel Y, Y_i = R_i' (null: the slot of mi_so3n_laplacian)
 };
+void mi::HandleDestroy::operator()(mi_so3n_cert *c) const { delete c; }
 
+// What is below `lazily made` appears when an entry point first needs it (TNT / GradientDescent users allocate none of the
+// least-squares, certificate, Laplacian or reweighting memory): who asks, what it is written from and what invalidates it
+// is the table of DESIGN.md 5.1 ("Lazily made state of mi_so3n"); the ensure_* functions are its only writers.
 struct mi_so3n {
   mi_ctx *ctx = nullptr;
   size_t N = 0, E = 0, nslices = 0, nnzb = 0, padded = 0;
-  long long *slice_ptr = nullptr;
-  int *perm = nullptr, *nbr = nullptr;
-  mi_vec *Dinv = nullptr;  // 9N (node order): the inverse diagonal blocks, the block-Jacobi preconditioner
-  double *Bblk = nullptr;                   // padded * 9
-  double *Sinc = nullptr, *winc = nullptr;  // padded * 9 (or * 4: sinc_quat), padded: per-incidence measurement and weight
-  bool sinc_quat = false;                   // Sinc holds unit quaternions (all measurements are rotations to rounding)
-  double *Dsl = nullptr;                    // nslices * 9 * 64: diagonal blocks in slice order
-  double *Rq = nullptr;                     // 4 N: unit quaternions of the point the NEXT assembly gathers from (r06; null:
-                                            // SO3_NO_RQUAT -- the assembly gathers R itself)
+  DevPtr<long long> slice_ptr;
+  DevPtr<int> perm, nbr;
+  Owned<mi_vec> Dinv;           // 9N (node order): the inverse diagonal blocks, the block-Jacobi preconditioner
+  DevPtr<double> Bblk;          // padded * 9
+  DevPtr<double> Sinc, winc;    // padded * 9 (or * 4: sinc_quat), padded: per-incidence measurement and weight
+  bool sinc_quat = false;       // Sinc holds unit quaternions (all measurements are rotations to rounding)
+  DevPtr<double> Dsl;           // nslices * 9 * 64: diagonal blocks in slice order
+  DevPtr<double> Rq;            // 4 N: unit quaternions of the point the NEXT assembly gathers from (r06; null:
+                                // SO3_NO_RQUAT -- the assembly gathers R itself)
   mi_op hess;
   mi_precon bj;
-  const mi_vec *R = nullptr;                // the point the model is bound to (mi_so3n_model) ...
-  uint64_t R_serial = 0;                    // ... by handle AND serial (mi::bound_to)
-  // mi_so3n_trial: the model assembled speculatively at the trial point (a second set of the arrays above plus the
-  // gradient), swapped in by the next mi_so3n_model call if that call is for the same vector -- keyed on the
-  // handle AND the identity of its contents (mi::VecKey), as in stiefel.hip
-  mi_vec *Dinv_next = nullptr, *grad_next = nullptr, *Hh = nullptr, *Pg = nullptr;
-  double *Bblk_next = nullptr, *Dsl_next = nullptr;
-  VecKey trial;
-  // mi_so3n_armijo_trial: the point whose GRADIENT ONLY sits in grad_next (the Hessian-sized _next arrays hold nothing,
-  // or the model of an older trial point: mi_so3n_model must not swap them in) -- a key of its own, same contents
-  // identity.  At most one of the two keys is live: whoever fills grad_next drops the other kind's.
-  VecKey armijo;
-  // q->Rq holds the quaternion records of THIS vector (written by the retraction of a fused trial step); cleared when
-  // the assembly converts another point into Rq.  mi_so3n_residual / mi_so3n_jacobian gather quaternions only then.
-  VecKey rq;
-  // ---- nonlinear least-squares view (mi_so3n_residual, mi_so3n_jacobian, mi_so3n_gn_scaling) ----
-  // host copies kept from creation; the device arrays appear when the residual or the Jacobian is first asked for
-  // (TNT / GradientDescent users pay no device memory)
-  std::vector<int32_t> h_ij;        // 2E: (i, j) per edge
-  std::vector<double> h_Se, h_w;    // E * (4 | 9) component-major measurement stream (as sinc_quat says); E weights
-  std::vector<uint32_t> h_slot;     // padded: edge << 1 | (the slot's node is the first node of the edge); padding 0
+  const mi_vec *R = nullptr;    // the point the model is bound to (mi_so3n_model) ...
+  uint64_t R_serial = 0;        // ... by handle AND serial (mi::bound_to)
+  // Keys, each the handle AND the identity of its contents (mi::VecKey).  trial: the point whose whole model sits in the
+  // _next arrays (mi_so3n_trial; swapped in by mi_so3n_model for the same vector); armijo: the point whose GRADIENT ONLY
+  // sits in grad_next (mi_so3n_armijo_trial) -- at most one of the two is live, whoever fills grad_next drops both;
+  // rq: the vector whose quaternion records Rq holds (written by the retraction of a fused trial step, cleared when the
+  // assembly converts another point into Rq; mi_so3n_residual / mi_so3n_jacobian gather quaternions only then).
+  VecKey trial, armijo, rq;
+  // host copies kept from creation for the first-use uploads
+  std::vector<int32_t> h_ij;      // 2E: (i, j) per edge
+  std::vector<double> h_Se, h_w;  // E * (4 | 9) component-major measurement stream (as sinc_quat says); E weights
+  std::vector<uint32_t> h_slot;   // padded: edge << 1 | (the slot's node is the first node of the edge); padding 0
   bool w_nonneg = true;
-  int2 *e_ij = nullptr;             // device, E
-  double *Se = nullptr, *swe = nullptr;  // device: E * (4 | 9), E
-  uint32_t *slot_edge = nullptr;    // device, padded (first mi_so3n_jacobian)
-  double *Jrot = nullptr;           // device, 9N: the rotations the bound dF / dF* read (4N used when jac_quat)
+  // ---- lazily made ----
+  Owned<mi_vec> grad_next;                 // 3N
+  Owned<mi_vec> Dinv_next, Hh, Pg;         // the trial arrays: 9N, 3N, 3N ...
+  DevPtr<double> Bblk_next, Dsl_next;      // ... and the second set of Bblk, Dsl
+  DevPtr<int2> e_ij;                       // the edge streams: E ...
+  DevPtr<double> Se;                       // ... E * (4 | 9)
+  DevPtr<double> swe;                      // E: sqrt(w_e) of the weights in force
+  DevPtr<uint32_t> slot_edge;              // the slot words: padded
+  DevPtr<double> Jrot;                     // 9N: the rotations the bound dF / dF* read (4N used when jac_quat)
   bool jac_quat = false;
   mi_op dF, dFt;
-  mi_vec *gn_diag = nullptr;        // 3N: 1 / sqrt(2 degw_i), each three times
-  mi_op *gn_op = nullptr;
-  mi_so3n_cert *cert = nullptr;     // mi_so3n_certificate: owned here, rebound by every call
-  mi_so3n_cert *lap = nullptr;      // mi_so3n_laplacian: a slot of its own (Y stays null), refreshed by every call
-  unsigned long long *round_words = nullptr;  // device, RW_WORDS: what mi_so3n_round / mi_so3n_project count
-  // ---- mi_so3n_reweight: device, E each, from the first reweighting on.  w_cur != nullptr <=> the weights in force are
-  // w_cur (what winc, swe and gn_diag were last written from), not h_w: every later first-use path reads it
-  double *w0 = nullptr, *w_cur = nullptr;
+  Owned<mi_vec> gn_diag;                   // 3N: 1 / sqrt(2 degw_i), each three times, of the weights in force
+  Owned<mi_op> gn_op;
+  Owned<mi_so3n_cert> cert;                // mi_so3n_certificate: rebound by every call
+  Owned<mi_so3n_cert> lap;                 // mi_so3n_laplacian: a slot of its own (Y stays null), refreshed by every call
+  DevPtr<unsigned long long> round_words;  // RW_WORDS: what mi_so3n_round / mi_so3n_project count
+  DevPtr<double> w0, w_cur;                // E each: the creation-time weights and, from the first reweighting on, the
+                                           // weights in force (what winc, swe and gn_diag were last written from)
 };
 
 namespace {
 
+static_assert(kSo3Window == (size_t)kBlock, "the degree-sorted window of so3_pack.h is the workgroup pass of k_bsr3_spmv");
 // workgroups of the model assembly: one per group of 4 slices while their objective partials fit 8 components of
 // kMaxRows rows (N <= 2.1e6 rotations), a grid-stride walk beyond
 constexpr int kModelComps = 8;
 static_assert(kCertComps == kModelComps, "k_so3_cert_diag lays its partial rows out as k_so3_model does");
 int model_grid(const mi_so3n *q) { return (int)std::min<size_t>((q->nslices + 3) / 4, (size_t)kModelComps * kMaxRows); }
-IncView view(const mi_so3n *q) {
-  return IncView{q->N, q->nslices, q->slice_ptr, q->perm, q->nbr};
+IncView view(const mi_so3n *q) { return IncView{q->N, q->nslices, q->slice_ptr.get(), q->perm.get(), q->nbr.get()}; }
+// a problem that gathers quaternions gets those of R into q->Rq (one pass over R) unless they are there already
+// (have_quat: the retraction of a trial step wrote them, or the rq key says so)
+void ensure_rq(mi_so3n *q, const double *R, bool have_quat) {
+  if (!q->Rq || have_quat) return;
+  q->rq.clear();  // (Rq is about to hold the conversion of a point given by address only)
+  hipLaunchKernelGGL(k_so3_quat, dim3(grid_for(q->ctx, q->N, 1)), dim3(256), 0, q->ctx->stream, q->N, R, q->Rq.get());
+}
+// what was worked out at another point or with other weights: the speculative trial model, the Armijo gradient and, for a
+// change of the weights, the bound model (the rq key describes a point, not the weights, and stays)
+void invalidate_models(mi_so3n *q, bool also_binding) {
+  q->trial.clear();
+  q->armijo.clear();
+  if (also_binding) q->R = nullptr, q->R_serial = 0;
 }
 // the assembly in one of its forms (SO3_OBJECTIVE: no outputs; SO3_GRAD: grad only), objective partials into ctx->partials2
-// have_quat: q->Rq already holds the quaternions of R (the trial step's retraction wrote them); otherwise they are formed
-// here first (one pass over R: a point the library did not produce -- the start, or the statement sequence's calls)
+// have_quat: see ensure_rq (a point the library did not produce -- the start, the statement sequence's calls -- is converted)
 void launch_assembly(mi_so3n *q, int form, int grid, const double *R, double *grad, double *Dinv, double *Bblk, double *Dsl,
                      bool have_quat = false) {
   mi_ctx *ctx = q->ctx;
   const bool gq = q->Rq != nullptr;
-  const double *Rq = q->Rq, *Sinc = q->Sinc, *winc = q->winc;
-  if (gq && !have_quat) q->rq.clear();  // (Rq is about to hold the conversion of a point given by address only)
-  if (gq && !have_quat)
-    hipLaunchKernelGGL(k_so3_quat, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, R, q->Rq);
+  const double *Rq = q->Rq.get(), *Sinc = q->Sinc.get(), *winc = q->winc.get();
+  ensure_rq(q, R, have_quat);
   DISPATCH_3(form, FORM, SO3_OBJECTIVE, SO3_MODEL, SO3_GRAD, DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(gq, GQ,
       if (FORM == SO3_GRAD) {
         KScope ks(ctx, MI_K_SO3_GRAD);
@@ -1118,14 +1110,17 @@ void launch_assembly(mi_so3n *q, int form, int grid, const double *R, double *gr
                            Sinc, winc, grad, Dinv, Bblk, Dsl, ctx->partials2);
       })));
 }
-// the objective partials the assembly left in ctx->partials2 -> one (all-reduced) sum in slots[0]
-int model_objective_to_slot(mi_so3n *q, int grid, double *slot) {
+// quantity `which` of the partial rows a pass of `grid` workgroups left in ctx->partials2 -> one (all-reduced) sum in
+// *slot.  0: the objective sum of the assembly in any of its forms and of k_so3_cert_diag; 1, 2: |Q - Q'|^2 and tr C of
+// k_so3_cert_diag
+int partial_rows_to_slot(mi_so3n *q, int grid, int which, double *slot) {
   mi_ctx *ctx = q->ctx;
+  const double *rows = ctx->partials2 + (size_t)which * kCertComps * kMaxRows;
   const int comps = (grid + kMaxRows - 1) / kMaxRows;
-  if (comps == 1) return reduce_rows_allreduce(ctx, ctx->partials2, grid, 1, slot);
+  if (comps == 1) return reduce_rows_allreduce(ctx, rows, grid, 1, slot);
   // (the rows of the last component past the last workgroup were zeroed by the kernel itself)
-  double *tmp = ctx->scalars + SLOT_RAW;  // (free outside mi_stiefel_gram)
-  MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, kMaxRows, comps, tmp));
+  double *tmp = ctx->scalars + SLOT_RAW + which * kCertComps;  // (free outside mi_stiefel_gram)
+  MI_TRY(reduce_rows_allreduce(ctx, rows, kMaxRows, comps, tmp));
   hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(1), 0, ctx->stream, (const double *)tmp, comps, slot);
   MI_HIP(hipGetLastError());
   return MI_OK;
@@ -1140,7 +1135,7 @@ int so3_apply_common(mi_op *self, const mi_vec *in, mi_vec *out, bool dots, int 
   constexpr bool nt = kBsr3NtDefault;
 #define BSR3(DV, NTV, STATE, PART)                                                                               \
   hipLaunchKernelGGL((k_bsr3_spmv<DV, NTV>), dim3(grid), dim3(kBlock), 0, ctx->stream, view(q), STATE,          \
-                     (const double *)q->Dsl, (const double *)q->Bblk, (const double *)in->d, out->d, PART)
+                     (const double *)q->Dsl.get(), (const double *)q->Bblk.get(), (const double *)in->d, out->d, PART)
   if (dots) {
     if (nt) BSR3(true, true, ctx->cg_live, ctx->partials); else BSR3(true, false, ctx->cg_live, ctx->partials);
   } else {
@@ -1153,15 +1148,25 @@ int so3_apply_common(mi_op *self, const mi_vec *in, mi_vec *out, bool dots, int 
   return MI_OK;
 }
 int so3_apply(mi_op *self, const mi_vec *in, mi_vec *out) { return so3_apply_common(self, in, out, false, nullptr); }
-int so3_apply_dots(mi_op *self, const mi_vec *in, mi_vec *out, int *np) {
-  return so3_apply_common(self, in, out, true, np);
-}
-int so3_bj_apply(mi_precon *self, const mi_vec *r, mi_vec *v) {
+int so3_apply_dots(mi_op *self, const mi_vec *in, mi_vec *out, int *np) { return so3_apply_common(self, in, out, true, np); }
+// v = D^-1 r by the library's block-Jacobi kernel, through a preconditioner made for the call
+int block3_apply(mi_ctx *ctx, const mi_vec *Dinv, const mi_vec *r, mi_vec *v) {
   mi_precon *tmp = nullptr;
-  MI_TRY(mi_precon_create_block3(self->ctx, ((mi_so3n *)self->impl)->Dinv, &tmp));
+  MI_TRY(mi_precon_create_block3(ctx, Dinv, &tmp));
   const int s = mi_precon_apply(tmp, r, v);
   mi_precon_destroy(tmp);
   return s;
+}
+int so3_bj_apply(mi_precon *self, const mi_vec *r, mi_vec *v) {
+  return block3_apply(self->ctx, ((mi_so3n *)self->impl)->Dinv.get(), r, v);
+}
+// an operator the problem lends out: mi_op_destroy on it is a no-op
+mi_op borrowed_op(mi_ctx *ctx, size_t n_in, size_t n_out, decltype(mi_op::apply) apply,
+                  decltype(mi_op::apply_sub_scaled) apply_sub_scaled, void *impl) {
+  mi_op op;
+  op.ctx = ctx, op.n = n_in, op.n_out = n_out, op.impl = impl, op.borrowed = true;
+  op.apply = apply, op.apply_sub_scaled = apply_sub_scaled;
+  return op;
 }
 
 // Y = R exp(hat xi) as a trial point: a problem that gathers quaternions gets those of Y in q->Rq from the same kernel
@@ -1170,7 +1175,7 @@ int retract_trial(mi_so3n *q, const mi_vec *R, const mi_vec *xi, mi_vec *Y) {
   if (!q->Rq) return mi_so3n_retract(q, R, xi, Y);
   touch(Y);
   hipLaunchKernelGGL(k_so3_retract<true>, dim3(grid_for(q->ctx, q->N, 1)), dim3(kBlock), 0, q->ctx->stream, q->N,
-                     (const double *)R->d, (const double *)xi->d, Y->d, q->Rq);
+                     (const double *)R->d, (const double *)xi->d, Y->d, q->Rq.get());
   MI_HIP(hipGetLastError());
   q->rq.set(Y);
   return MI_OK;
@@ -1183,11 +1188,30 @@ int trial_tail(mi_so3n *q, int form, const mi_vec *R_trial, double *Dinv, double
                int g2_slot) {
   mi_ctx *ctx = q->ctx;
   const int grid = model_grid(q);
-  launch_assembly(q, form, grid, R_trial->d, q->grad_next->d, Dinv, Bblk, Dsl, q->Rq != nullptr);
+  launch_assembly(q, form, grid, R_trial->d, q->grad_next->d, Dinv, Bblk, Dsl, /*have_quat=*/true);
   MI_HIP(hipGetLastError());
-  MI_TRY(model_objective_to_slot(q, grid, ctx->scalars + f_slot));
+  MI_TRY(partial_rows_to_slot(q, grid, 0, ctx->scalars + f_slot));
   const double *gn[1] = {q->grad_next->d};
   return dot_batch_to_slots(ctx, 1, gn, gn, 3 * q->N, g2_slot);
+}
+
+// ---- the lazily made resources: one ensure_* per group.  Each is idempotent and builds into locals, so a
+// failure leaves q as it was. ----
+// grad_next (3N): the gradient at the trial point of mi_so3n_trial / mi_so3n_armijo_trial; read by mi_so3n_model / _gradient
+int ensure_grad_next(mi_so3n *q) { return q->grad_next ? MI_OK : vec_alloc(q->ctx, 3 * q->N, q->grad_next); }
+// the trial arrays (the model's second set + Hess h + M^-1 grad): written by mi_so3n_trial, swapped in by mi_so3n_model
+int ensure_trial_arrays(mi_so3n *q) {
+  if (q->Dinv_next) return MI_OK;
+  Owned<mi_vec> Dinv, Hh, Pg;
+  DevPtr<double> Bblk, Dsl;
+  MI_TRY(vec_alloc(q->ctx, 9 * q->N, Dinv));
+  MI_TRY(vec_alloc(q->ctx, 3 * q->N, Hh));
+  MI_TRY(vec_alloc(q->ctx, 3 * q->N, Pg));
+  MI_TRY(dev_alloc(Bblk, q->padded * 9));
+  MI_TRY(dev_alloc(Dsl, q->nslices * 9 * 64));
+  q->Dinv_next = std::move(Dinv), q->Hh = std::move(Hh), q->Pg = std::move(Pg);
+  q->Bblk_next = std::move(Bblk), q->Dsl_next = std::move(Dsl);
+  return MI_OK;
 }
 
 }  // namespace
@@ -1197,201 +1221,35 @@ extern "C" {
 int mi_so3n_create(mi_ctx *ctx, size_t N, size_t E, const int32_t *ei, const int32_t *ej, const double *Rt,
                    const double *w, mi_so3n **out) {
   MI_REQUIRE(ctx && out && (E == 0 || (ei && ej && Rt && w)), "null argument");
-  MI_REQUIRE(N > 0 && N < (size_t)INT32_MAX, "bad number of rotations");
-  for (size_t e = 0; e < E; ++e)
-    MI_REQUIRE(ei[e] >= 0 && (size_t)ei[e] < N && ej[e] >= 0 && (size_t)ej[e] < N && ei[e] != ej[e],
-               "edge %zu has invalid endpoints", e);
-  // incidence lists: node -> (neighbour, edge, direction), in edge order
-  std::vector<std::vector<int>> lists(N);
-  for (size_t e = 0; e < E; ++e) {
-    lists[(size_t)ej[e]].push_back((int)e + 1);      // head: +(e+1)
-    lists[(size_t)ei[e]].push_back(-((int)e + 1));   // tail: -(e+1)
-  }
-  // Experiment switch SO3_SORT_NBR (r04, VERDICT item 3: "incidences ordered in column phases"): every node's incidences
-  // in ascending order of the NEIGHBOUR instead of edge order.  The whole product is one resident set of waves (N / 64
-  // waves, one node per lane) that start together and walk their incidence slots at the same pace, so slot k of every
-  // row then points into the same quantile region of xi at about the same time -- the chance that a chord gather finds
-  // its 128-byte line in the XCD's 4 MB L2 should rise.  Measured in DESIGN 5.1; changes the order of a row's sum.
-  if (ctx->cfg.so3_sort_nbr)
-    for (size_t i = 0; i < N; ++i)
-      std::stable_sort(lists[i].begin(), lists[i].end(), [&](int a, int b) {
-        const int ea = std::abs(a) - 1, eb = std::abs(b) - 1;
-        const int ja = a > 0 ? ei[ea] : ej[ea], jb = b > 0 ? ei[eb] : ej[eb];
-        return ja < jb;
-      });
-  // SELL-64-sigma, sigma = kBlock = the 1024 nodes one workgroup pass owns: inside each window the
-  // nodes are ordered by descending degree (stable), so a slice's 64 nodes have near-equal degree
-  // and the padding of an irregular pose graph drops from ~1.66x to ~1.05x of the incidences.  The
-  // window is a contiguous node range, so x_i loads / h_i stores stay inside one 24 KB span per
-  // workgroup pass; tangent vectors keep the caller's node order.
-  const size_t nslices = (N + 63) / 64;
-  std::vector<int> perm(nslices * 64, -1);
-  for (size_t w0 = 0; w0 < N; w0 += kBlock) {
-    const size_t w1 = std::min(N, w0 + kBlock);
-    std::vector<int> ids(w1 - w0);
-    for (size_t i = w0; i < w1; ++i) ids[i - w0] = (int)i;
-    std::stable_sort(ids.begin(), ids.end(),
-                     [&](int a, int b) { return lists[(size_t)a].size() > lists[(size_t)b].size(); });
-    for (size_t i = w0; i < w1; ++i) perm[i] = ids[i - w0];
-  }
-  std::vector<long long> sp(nslices + 1, 0);
-  for (size_t s = 0; s < nslices; ++s) {
-    size_t wmax = 0;
-    for (size_t l = s * 64; l < (s + 1) * 64; ++l)
-      if (perm[l] >= 0) wmax = std::max(wmax, lists[(size_t)perm[l]].size());
-    sp[s + 1] = sp[s] + (long long)wmax;
-  }
-  const size_t padded = (size_t)sp[nslices] * 64;
-  std::vector<int> nbr(padded), edge(padded, -1);
-  std::vector<signed char> dir(padded, 0);
-  size_t nnzb = 0;
-  for (size_t s = 0; s < nslices; ++s)
-    for (int lane = 0; lane < 64; ++lane) {
-      const bool owned = perm[s * 64 + lane] >= 0;
-      const size_t i = owned ? (size_t)perm[s * 64 + lane] : N - 1;
-      for (long long k = 0; k < sp[s + 1] - sp[s]; ++k) {
-        const size_t e0 = (size_t)(sp[s] + k) * 64 + lane;
-        nbr[e0] = (int)i;
-        if (owned && (size_t)k < lists[i].size()) {
-          const int code = lists[i][(size_t)k];
-          const int e = std::abs(code) - 1;
-          edge[e0] = e;
-          dir[e0] = code > 0 ? 1 : -1;
-          nbr[e0] = code > 0 ? ei[e] : ej[e];
-          ++nnzb;
-        }
-      }
-    }
-  // the measurement and weight of every incidence in slot order (k_so3_model streams them)
-  // ... the measurements as unit quaternions when every one of them is a rotation to rounding (k_so3_model<., SQ>)
-  bool all_rot = !ctx->cfg.so3_no_quat;
-  for (size_t e = 0; e < E && all_rot; ++e) {
-    const double *M = Rt + 9 * e;
-    for (int a = 0; a < 3 && all_rot; ++a)
-      for (int b = 0; b < 3; ++b) {
-        const double d = M[a] * M[b] + M[3 + a] * M[3 + b] + M[6 + a] * M[6 + b] - (a == b ? 1.0 : 0.0);
-        if (!(std::fabs(d) <= 1e-13)) all_rot = false;
-      }
-    const double det = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-    if (!(det > 0)) all_rot = false;
-  }
-  auto to_quat = [](const double *M, double *qv) {  // Shepperd's branch on the largest of (trace, m00, m11, m22)
-    const double tr = M[0] + M[4] + M[8];
-    double w, x, y, z;
-    if (tr >= M[0] && tr >= M[4] && tr >= M[8]) {
-      w = 1 + tr; x = M[7] - M[5]; y = M[2] - M[6]; z = M[3] - M[1];
-    } else if (M[0] >= M[4] && M[0] >= M[8]) {
-      w = M[7] - M[5]; x = 1 + M[0] - M[4] - M[8]; y = M[1] + M[3]; z = M[2] + M[6];
-    } else if (M[4] >= M[8]) {
-      w = M[2] - M[6]; x = M[1] + M[3]; y = 1 - M[0] + M[4] - M[8]; z = M[5] + M[7];
-    } else {
-      w = M[3] - M[1]; x = M[2] + M[6]; y = M[5] + M[7]; z = 1 - M[0] - M[4] + M[8];
-    }
-    const double nrm = std::sqrt(w * w + x * x + y * y + z * z);
-    qv[0] = w / nrm; qv[1] = x / nrm; qv[2] = y / nrm; qv[3] = z / nrm;
-  };
-  const int scomp = all_rot ? 4 : 9;
-  std::vector<double> sinc(std::max<size_t>(1, padded * scomp), 0.0), winc(std::max<size_t>(1, padded), 0.0);
-  for (size_t s = 0; s < nslices; ++s)
-    for (long long k = sp[s]; k < sp[s + 1]; ++k)
-      for (int lane = 0; lane < 64; ++lane) {
-        const size_t e0 = (size_t)k * 64 + lane;
-        const int e = edge[e0];
-        if (e < 0) continue;
-        winc[e0] = w[e];
-        double Sm[9];
-        for (int r = 0; r < 3; ++r)
-          for (int c = 0; c < 3; ++c) Sm[r * 3 + c] = dir[e0] > 0 ? Rt[9 * (size_t)e + r * 3 + c] : Rt[9 * (size_t)e + c * 3 + r];
-        if (all_rot) {
-          double qv[4];
-          to_quat(Sm, qv);
-          for (int c = 0; c < 4; ++c) sinc[((size_t)k * 4 + c) * 64 + lane] = qv[c];
-        } else {
-          for (int c = 0; c < 9; ++c) sinc[((size_t)k * 9 + c) * 64 + lane] = Sm[c];
-        }
-      }
-  mi_so3n *q = new mi_so3n();
-  // what the least-squares view uploads on first use: end points, weights, the per-edge measurement stream in the form
-  // of Sinc (the same conversion: a second node's slot and the edge stream expand to the same bits), the slot words
-  q->h_ij.resize(2 * E);
-  q->h_w.assign(w, w + E);
-  q->h_Se.resize(E * (size_t)scomp);
-  for (size_t e = 0; e < E; ++e) {
-    q->h_ij[2 * e] = ei[e];
-    q->h_ij[2 * e + 1] = ej[e];
-    if (!(w[e] >= 0)) q->w_nonneg = false;
-    double qv[9];
-    if (all_rot) to_quat(Rt + 9 * e, qv);
-    else std::memcpy(qv, Rt + 9 * e, 9 * sizeof(double));
-    for (int c = 0; c < scomp; ++c) q->h_Se[(size_t)c * E + e] = qv[c];
-  }
-  q->h_slot.assign(padded, 0u);
-  if (E < ((size_t)1 << 31))
-    for (size_t e0 = 0; e0 < padded; ++e0)
-      if (edge[e0] >= 0) q->h_slot[e0] = ((uint32_t)edge[e0] << 1) | (dir[e0] < 0 ? 1u : 0u);
+  So3Pack P;
+  std::string err;
+  MI_REQUIRE(so3_pack(N, E, ei, ej, Rt, w, ctx->cfg.so3_no_quat, ctx->cfg.so3_sort_nbr != 0, P, err) == 0, "%s", err.c_str());
+  auto q = std::make_unique<mi_so3n>();
   q->ctx = ctx;
-  q->N = N;
-  q->E = E;
-  q->nslices = nslices;
-  q->nnzb = nnzb;
-  q->padded = padded;
-  q->sinc_quat = all_rot;
-  MI_TRY(upload((void **)&q->slice_ptr, sp.data(), sp.size() * sizeof(long long)));
-  MI_TRY(upload((void **)&q->perm, perm.data(), perm.size() * sizeof(int)));
-  MI_HIP(hipMalloc((void **)&q->Dsl, nslices * 9 * 64 * sizeof(double)));
-  if (!ctx->cfg.so3_no_rquat) MI_HIP(hipMalloc((void **)&q->Rq, std::max<size_t>(1, N) * 4 * sizeof(double)));
-  MI_TRY(upload((void **)&q->nbr, nbr.data(), padded * sizeof(int)));
-  MI_HIP(hipMalloc((void **)&q->Bblk, std::max<size_t>(1, padded * 9) * sizeof(double)));
-  MI_TRY(upload((void **)&q->Sinc, sinc.data(), sinc.size() * sizeof(double)));
-  MI_TRY(upload((void **)&q->winc, winc.data(), winc.size() * sizeof(double)));
-  MI_TRY(mi_vec_create(ctx, 9 * N, &q->Dinv));
-  q->hess.ctx = ctx;
-  q->hess.n = 3 * N;
-  q->hess.apply = so3_apply;
+  q->N = N, q->E = E, q->nslices = P.nslices, q->nnzb = P.nnzb, q->padded = P.padded;
+  q->sinc_quat = P.sinc_quat, q->w_nonneg = P.w_nonneg;
+  MI_TRY(dev_upload(q->slice_ptr, P.slice_ptr.data(), P.slice_ptr.size()));
+  MI_TRY(dev_upload(q->perm, P.perm.data(), P.perm.size()));
+  MI_TRY(dev_alloc(q->Dsl, P.nslices * 9 * 64));
+  if (!ctx->cfg.so3_no_rquat) MI_TRY(dev_alloc(q->Rq, N * 4));
+  MI_TRY(dev_upload(q->nbr, P.nbr.data(), P.padded));
+  MI_TRY(dev_alloc(q->Bblk, P.padded * 9));
+  MI_TRY(dev_upload(q->Sinc, P.sinc.data(), P.sinc.size()));
+  MI_TRY(dev_upload(q->winc, P.winc.data(), P.winc.size()));
+  MI_TRY(vec_alloc(ctx, 9 * N, q->Dinv));
+  // what the least-squares view and the reweighting upload on first use
+  q->h_ij = std::move(P.h_ij), q->h_Se = std::move(P.h_Se), q->h_w = std::move(P.h_w), q->h_slot = std::move(P.h_slot);
+  q->hess = borrowed_op(ctx, 3 * N, 0, so3_apply, nullptr, q.get());
   q->hess.apply_dots = so3_apply_dots;
-  q->hess.impl = q;
-  q->hess.borrowed = true;
-  q->bj.ctx = ctx;
-  q->bj.n = 3 * N;
-  q->bj.kind = 2;  // fusable 3x3 block-Jacobi: data = inverse blocks
-  q->bj.data = q->Dinv->d;
-  q->bj.apply = so3_bj_apply;
-  q->bj.impl = q;
-  q->bj.borrowed = true;
-  *out = q;
+  q->bj.ctx = ctx, q->bj.n = 3 * N, q->bj.impl = q.get(), q->bj.borrowed = true;
+  q->bj.kind = 2, q->bj.data = q->Dinv->d, q->bj.apply = so3_bj_apply;  // fusable 3x3 block-Jacobi: data = inverse blocks
+  *out = q.release();
   return MI_OK;
 }
 
 int mi_so3n_destroy(mi_so3n *q) {
   if (!q) return MI_OK;
   (void)hipStreamSynchronize(q->ctx->stream);
-  (void)hipFree(q->slice_ptr); (void)hipFree(q->nbr);
-  (void)hipFree(q->Bblk); (void)hipFree(q->perm); (void)hipFree(q->Dsl);
-  if (q->Rq) (void)hipFree(q->Rq);
-  (void)hipFree(q->Sinc); (void)hipFree(q->winc);
-  (void)hipFree(q->Bblk_next); (void)hipFree(q->Dsl_next);
-  mi_vec_destroy(q->Dinv);
-  mi_vec_destroy(q->Dinv_next);
-  mi_vec_destroy(q->grad_next);
-  mi_vec_destroy(q->Hh);
-  mi_vec_destroy(q->Pg);
-  (void)hipFree(q->e_ij); (void)hipFree(q->Se); (void)hipFree(q->swe); (void)hipFree(q->slot_edge); (void)hipFree(q->Jrot);
-  (void)hipFree(q->w0); (void)hipFree(q->w_cur);
-  if (q->gn_op) {
-    q->gn_op->borrowed = false;
-    mi_op_destroy(q->gn_op);
-  }
-  mi_vec_destroy(q->gn_diag);
-  if (q->cert) {
-    (void)hipFree(q->cert->Esl);
-    mi_vec_destroy(q->cert->Y);
-    delete q->cert;
-  }
-  if (q->lap) {
-    (void)hipFree(q->lap->Esl);
-    delete q->lap;
-  }
-  (void)hipFree(q->round_words);
   delete q;
   return MI_OK;
 }
@@ -1419,7 +1277,7 @@ int mi_so3n_objective(mi_so3n *q, const mi_vec *R, double *f) {
   const int grid = model_grid(q);
   launch_assembly(q, SO3_OBJECTIVE, grid, R->d, nullptr, nullptr, nullptr, nullptr);
   MI_HIP(hipGetLastError());
-  MI_TRY(model_objective_to_slot(q, grid, ctx->scalars + SLOT_MISC));
+  MI_TRY(partial_rows_to_slot(q, grid, 0, ctx->scalars + SLOT_MISC));
   double s = 0;
   MI_TRY(read_slots_sync(ctx, SLOT_MISC, 1, &s));
   *f = .25 * s;  // (every edge from both ends)
@@ -1431,7 +1289,6 @@ int mi_so3n_model(mi_so3n *q, const mi_vec *R, mi_vec *grad, mi_op **hess, mi_pr
   MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
   MI_REQUIRE(grad->n == 3 * q->N, "gradient must hold 3N doubles");
   touch(grad);
-  mi_ctx *ctx = q->ctx;
   if (q->trial.is(R)) {
     // R is the point mi_so3n_trial just evaluated: its model exists already
     // (the point of an Armijo trial is NOT one: only its gradient exists -- the full assembly below)
@@ -1439,13 +1296,12 @@ int mi_so3n_model(mi_so3n *q, const mi_vec *R, mi_vec *grad, mi_op **hess, mi_pr
     std::swap(q->Bblk, q->Bblk_next);
     std::swap(q->Dsl, q->Dsl_next);
     q->bj.data = q->Dinv->d;
-    MI_TRY(mi_vec_copy(grad, q->grad_next));
+    MI_TRY(mi_vec_copy(grad, q->grad_next.get()));
   } else {
-    launch_assembly(q, SO3_MODEL, model_grid(q), R->d, grad->d, q->Dinv->d, q->Bblk, q->Dsl);
+    launch_assembly(q, SO3_MODEL, model_grid(q), R->d, grad->d, q->Dinv->d, q->Bblk.get(), q->Dsl.get());
     MI_HIP(hipGetLastError());
   }
-  q->trial.clear();
-  q->armijo.clear();
+  invalidate_models(q, false);
   q->R = R;
   q->R_serial = R->serial;
   if (hess) *hess = &q->hess;
@@ -1479,18 +1335,11 @@ int mi_so3n_trial(mi_so3n *q, const mi_vec *R, const mi_vec *h, const mi_vec *g,
   mi_ctx *ctx = q->ctx;
   ctx->fusion.fused_trial_steps++;
   const size_t N3 = 3 * q->N;
-  if (!q->grad_next) MI_TRY(mi_vec_create(ctx, N3, &q->grad_next));  // (shared with mi_so3n_armijo_trial)
-  if (!q->Dinv_next) {
-    MI_TRY(mi_vec_create(ctx, 9 * q->N, &q->Dinv_next));
-    MI_TRY(mi_vec_create(ctx, N3, &q->Hh));
-    MI_TRY(mi_vec_create(ctx, N3, &q->Pg));
-    MI_HIP(hipMalloc((void **)&q->Bblk_next, std::max<size_t>(1, q->padded * 9) * sizeof(double)));
-    MI_HIP(hipMalloc((void **)&q->Dsl_next, q->nslices * 9 * 64 * sizeof(double)));
-  }
-  q->trial.clear();
-  q->armijo.clear();  // (grad_next is about to be overwritten)
+  MI_TRY(ensure_grad_next(q));
+  MI_TRY(ensure_trial_arrays(q));
+  invalidate_models(q, false);  // (grad_next is about to be overwritten)
   // (a) Hess h, then |h|^2, <g,h>, <h, Hess h> in one pass (as MI355::dot_batch does)
-  MI_TRY(so3_apply(&q->hess, h, q->Hh));
+  MI_TRY(so3_apply(&q->hess, h, q->Hh.get()));
   {
     const double *xs[3] = {h->d, g->d, h->d}, *ys[3] = {h->d, h->d, q->Hh->d};
     MI_TRY(dot_batch_to_slots(ctx, 3, xs, ys, N3, SLOT_MISC));
@@ -1499,13 +1348,9 @@ int mi_so3n_trial(mi_so3n *q, const mi_vec *R, const mi_vec *h, const mi_vec *g,
   MI_TRY(retract_trial(q, R, h, R_trial));
   // (c) + (d) the model at R+ into the second set of arrays, with f(R+) from the same pass (r05: the objective was an
   // edge pass of its own, 61 us and 416 MB at the fabric), and |grad f(R+)|^2
-  MI_TRY(trial_tail(q, SO3_MODEL, R_trial, q->Dinv_next->d, q->Bblk_next, q->Dsl_next, SLOT_MISC + 3, SLOT_MISC + 4));
+  MI_TRY(trial_tail(q, SO3_MODEL, R_trial, q->Dinv_next->d, q->Bblk_next.get(), q->Dsl_next.get(), SLOT_MISC + 3, SLOT_MISC + 4));
   if (with_precon) {
-    mi_precon *tmp = nullptr;
-    MI_TRY(mi_precon_create_block3(ctx, q->Dinv_next, &tmp));
-    const int s = mi_precon_apply(tmp, q->grad_next, q->Pg);
-    mi_precon_destroy(tmp);
-    MI_TRY(s);
+    MI_TRY(block3_apply(ctx, q->Dinv_next.get(), q->grad_next.get(), q->Pg.get()));
     const double *xs[1] = {q->Pg->d}, *ys[1] = {q->Pg->d};
     MI_TRY(dot_batch_to_slots(ctx, 1, xs, ys, N3, SLOT_MISC + 5));
   }
@@ -1540,7 +1385,7 @@ int mi_so3n_gradient(mi_so3n *q, const mi_vec *R, mi_vec *grad) {
   if (q->armijo.is(R) || q->trial.is(R)) {
     // the last Armijo trial (or, speculatively, the last trust-region trial) evaluated this very point: its gradient is
     // there.  Neither key is consumed: a following mi_so3n_model(R) still finds the speculative model of a TNT trial.
-    return mi_vec_copy(grad, q->grad_next);
+    return mi_vec_copy(grad, q->grad_next.get());
   }
   touch(grad);
   launch_assembly(q, SO3_GRAD, model_grid(q), R->d, grad->d, nullptr, nullptr, nullptr);
@@ -1558,10 +1403,8 @@ int mi_so3n_armijo_trial(mi_so3n *q, const mi_vec *R, const mi_vec *g, double t,
   MI_REQUIRE(h_out->d != g->d, "the step must not alias the gradient");
   mi_ctx *ctx = q->ctx;
   ctx->fusion.fused_trial_steps++;
-  const size_t N3 = 3 * q->N;
-  if (!q->grad_next) MI_TRY(mi_vec_create(ctx, N3, &q->grad_next));  // (none of the Hessian-sized _next arrays)
-  q->trial.clear();  // (grad_next is about to be overwritten: the speculative model loses its gradient)
-  q->armijo.clear();
+  MI_TRY(ensure_grad_next(q));  // (none of the Hessian-sized trial arrays)
+  invalidate_models(q, false);  // (grad_next is about to be overwritten: the speculative model loses its gradient)
   // (a) h = -t g: the kernel of DeviceVector's `-t * g` (mi_vec_scale_to), then R+ = R exp(hat h)
   MI_TRY(mi_vec_scale_to(h_out, -t, g));
   MI_TRY(retract_trial(q, R, h_out, R_trial));
@@ -1584,52 +1427,96 @@ int edge_grid(const mi_so3n *q) {
   return (int)std::min<size_t>(std::max<size_t>(1, (q->E + kNlsBlock - 1) / kNlsBlock), (size_t)kMaxRows);
 }
 int node_grid(const mi_so3n *q) { return (int)std::min<size_t>(std::max<size_t>(1, (q->nslices + 3) / 4), (size_t)kMaxRows); }
-// the static per-edge streams (end points, measurement) and the incidence -> edge words, on first use
-int edge_upload(mi_so3n *q) {
-  if (q->e_ij) return MI_OK;
-  MI_TRY(upload((void **)&q->Se, q->h_Se.data(), q->h_Se.size() * sizeof(double)));
-  MI_TRY(upload((void **)&q->e_ij, q->h_ij.data(), q->h_ij.size() * sizeof(int32_t)));
-  return MI_OK;
-}
-int slot_upload(mi_so3n *q) {
-  if (q->slot_edge) return MI_OK;
-  MI_REQUIRE(q->E < ((size_t)1 << 31), "the incidence -> edge words hold edge numbers below 2^31");
-  return upload((void **)&q->slot_edge, q->h_slot.data(), q->h_slot.size() * sizeof(uint32_t));
-}
-// the edge streams of the least-squares view, on first use; sqrt(w_e) from the weights in force (after a reweighting: the
-// device's, mi_so3n::w_cur)
-int nls_upload(mi_so3n *q, bool with_slots) {
-  MI_REQUIRE(q->w_nonneg, "the least-squares form F_e = sqrt(w_e) (R_j - R_i Rt_e) needs weights >= 0");
-  MI_REQUIRE(!q->ctx->uniform_grid, "the least-squares view of mi_so3n is single-context");
-  MI_TRY(edge_upload(q));
-  if (!q->swe) {
-    if (q->w_cur) {
-      MI_HIP(hipMalloc((void **)&q->swe, std::max<size_t>(1, q->E) * sizeof(double)));
-      hipLaunchKernelGGL(k_so3_sqrt_w, dim3(edge_grid(q)), dim3(kNlsBlock), 0, q->ctx->stream, q->E, (const double *)q->w_cur,
-                         q->swe);
-      MI_HIP(hipGetLastError());
-    } else {
-      std::vector<double> sw(q->E);
-      for (size_t e = 0; e < q->E; ++e) sw[e] = std::sqrt(q->h_w[e]);
-      MI_TRY(upload((void **)&q->swe, sw.data(), sw.size() * sizeof(double)));
-    }
-  }
-  if (with_slots) {
-    MI_TRY(slot_upload(q));
-    if (!q->Jrot) MI_HIP(hipMalloc((void **)&q->Jrot, q->N * 9 * sizeof(double)));
-  }
-  return MI_OK;
-}
-// winc (and gn_diag when it exists) from the per-edge weights w_cur
-int launch_inc_reweight(mi_so3n *q) {
+EdgeView edge_view(const mi_so3n *q) { return EdgeView{q->E, q->e_ij.get(), q->Se.get(), q->swe.get()}; }
+// winc, and gn_diag (may be null), from the per-edge weights w_cur
+int launch_inc_reweight(mi_so3n *q, double *gn_diag) {
   mi_ctx *ctx = q->ctx;
   KScope ks(ctx, MI_K_SO3_INC_REWEIGHT);
   hipLaunchKernelGGL(k_so3_inc_reweight, dim3(node_grid(q)), dim3(kNlsBlock), 0, ctx->stream, view(q),
-                     (const uint32_t *)q->slot_edge, (const double *)q->w_cur, q->winc, q->gn_diag ? q->gn_diag->d : nullptr);
+                     (const uint32_t *)q->slot_edge.get(), (const double *)q->w_cur.get(), q->winc.get(), gn_diag);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
-EdgeView edge_view(const mi_so3n *q) { return EdgeView{q->E, q->e_ij, q->Se, q->swe}; }
+// the edge streams e_ij, Se (static): read by k_so3_residual, k_so3_jac, k_so3_edge_weight
+int ensure_edge_streams(mi_so3n *q) {
+  if (q->e_ij) return MI_OK;
+  DevPtr<double> Se; DevPtr<int2> ij;
+  MI_TRY(dev_upload(Se, q->h_Se.data(), q->h_Se.size()));
+  MI_TRY(dev_upload(ij, (const int2 *)q->h_ij.data(), q->E));
+  q->Se = std::move(Se), q->e_ij = std::move(ij);
+  return MI_OK;
+}
+// the slot words slot_edge (static): read by k_so3_jact, k_so3_inc_reweight
+int ensure_slot_words(mi_so3n *q) {
+  if (q->slot_edge) return MI_OK;
+  MI_REQUIRE(q->E < ((size_t)1 << 31), "the incidence -> edge words hold edge numbers below 2^31");
+  return dev_upload(q->slot_edge, q->h_slot.data(), q->h_slot.size());
+}
+// The weights in force are w_cur on the device once a reweighting has made it, else h_w on the host: ensure_swe and
+// ensure_gn_scaling are the two places that decide between them (a reweighting rewrites what exists of both itself).
+// swe = sqrt(w_e): read by k_so3_residual, k_so3_jac; rewritten by k_so3_edge_weight
+int ensure_swe(mi_so3n *q) {
+  if (q->swe) return MI_OK;
+  DevPtr<double> swe;
+  if (q->w_cur) {
+    MI_TRY(dev_alloc(swe, q->E));
+    hipLaunchKernelGGL(k_so3_sqrt_w, dim3(edge_grid(q)), dim3(kNlsBlock), 0, q->ctx->stream, q->E, (const double *)q->w_cur.get(),
+                       swe.get());
+    MI_HIP(hipGetLastError());
+  } else {
+    std::vector<double> sw(q->E);
+    for (size_t e = 0; e < q->E; ++e) sw[e] = std::sqrt(q->h_w[e]);
+    MI_TRY(dev_upload(swe, sw.data(), sw.size()));
+  }
+  q->swe = std::move(swe);
+  return MI_OK;
+}
+// gn_diag = 1 / sqrt(2 degw_i) and the diagonal operator on it (mi_so3n_gn_scaling); rewritten by k_so3_inc_reweight
+int ensure_gn_scaling(mi_so3n *q) {
+  if (q->gn_op) return MI_OK;
+  Owned<mi_vec> diag;
+  MI_TRY(vec_alloc(q->ctx, 3 * q->N, diag));
+  if (q->w_cur) {
+    // by the pass that keeps it current (winc is rewritten to itself)
+    touch(diag.get());
+    MI_TRY(launch_inc_reweight(q, diag->d));
+  } else {
+    std::vector<double> degw(q->N, 0.0), d(3 * q->N);
+    for (size_t e = 0; e < q->E; ++e) {
+      degw[(size_t)q->h_ij[2 * e]] += q->h_w[e];
+      degw[(size_t)q->h_ij[2 * e + 1]] += q->h_w[e];
+    }
+    for (size_t i = 0; i < q->N; ++i) d[3 * i] = d[3 * i + 1] = d[3 * i + 2] = degw[i] > 0 ? 1.0 / std::sqrt(2 * degw[i]) : 1.0;
+    MI_TRY(mi_vec_upload(diag.get(), d.data(), d.size()));
+  }
+  mi_op *op = nullptr;
+  MI_TRY(mi_op_create_diag(q->ctx, diag.get(), &op));
+  op->borrowed = true;
+  q->gn_diag = std::move(diag);
+  q->gn_op.reset(op);
+  return MI_OK;
+}
+// Jrot (9N): written by mi_so3n_jacobian, read by k_so3_jac, k_so3_jact
+int ensure_jrot(mi_so3n *q) { return q->Jrot ? MI_OK : dev_alloc(q->Jrot, q->N * 9); }
+// w0 (the creation-time weights) and w_cur (written by k_so3_edge_weight): mi_so3n_reweight
+int ensure_weights(mi_so3n *q) {
+  if (q->w_cur) return MI_OK;
+  DevPtr<double> w0, w_cur;
+  MI_TRY(dev_upload(w0, q->h_w.data(), q->E));
+  MI_TRY(dev_alloc(w_cur, q->E));
+  q->w0 = std::move(w0), q->w_cur = std::move(w_cur);
+  return MI_OK;
+}
+// what mi_so3n_residual (and, with_jacobian, mi_so3n_jacobian) reads
+int ensure_nls(mi_so3n *q, bool with_jacobian) {
+  MI_REQUIRE(q->w_nonneg, "the least-squares form F_e = sqrt(w_e) (R_j - R_i Rt_e) needs weights >= 0");
+  MI_REQUIRE(!q->ctx->uniform_grid, "the least-squares view of mi_so3n is single-context");
+  MI_TRY(ensure_edge_streams(q));
+  MI_TRY(ensure_swe(q));
+  if (with_jacobian) MI_TRY(ensure_slot_words(q));
+  if (with_jacobian) MI_TRY(ensure_jrot(q));
+  return MI_OK;
+}
 
 int so3_jac_launch(mi_op *self, const mi_vec *in, mi_vec *out, const double *scale, const int *mode, const int *gate,
                    double *partials, int *nparts) {
@@ -1640,7 +1527,7 @@ int so3_jac_launch(mi_op *self, const mi_vec *in, mi_vec *out, const double *sca
   KScope ks(ctx, MI_K_SO3_JAC);
   DISPATCH_FLAG(fused, FUSED, DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(q->jac_quat, GQ,
       hipLaunchKernelGGL((k_so3_jac<FUSED, SQ, GQ>), dim3(grid), dim3(kNlsBlock), 0, ctx->stream, edge_view(q),
-                         (const double *)q->Jrot, (const double *)in->d, out->d, scale, mode, gate, partials))));
+                         (const double *)q->Jrot.get(), (const double *)in->d, out->d, scale, mode, gate, partials))));
   if (nparts) *nparts = grid;
   MI_HIP(hipGetLastError());
   return MI_OK;
@@ -1654,8 +1541,8 @@ int so3_jact_launch(mi_op *self, const mi_vec *in, mi_vec *out, const double *sc
   KScope ks(ctx, MI_K_SO3_JACT);
   DISPATCH_FLAG(fused, FUSED, DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(q->jac_quat, GQ,
       hipLaunchKernelGGL((k_so3_jact<FUSED, SQ, GQ>), dim3(grid), dim3(kNlsBlock), 0, ctx->stream, view(q),
-                         (const double *)q->Jrot, (const double *)q->Sinc, (const double *)q->winc,
-                         (const uint32_t *)q->slot_edge, (const double *)in->d, out->d, scale, mode, gate, partials))));
+                         (const double *)q->Jrot.get(), (const double *)q->Sinc.get(), (const double *)q->winc.get(),
+                         (const uint32_t *)q->slot_edge.get(), (const double *)in->d, out->d, scale, mode, gate, partials))));
   if (nparts) *nparts = grid;
   MI_HIP(hipGetLastError());
   return MI_OK;
@@ -1690,7 +1577,7 @@ int mi_so3n_residual(mi_so3n *q, const mi_vec *R, mi_vec *F, double *sqnorm) {
     if (sqnorm) *sqnorm = 0;
     return MI_OK;
   }
-  MI_TRY(nls_upload(q, false));
+  MI_TRY(ensure_nls(q, false));
   touch(F);
   // quaternion gathers only at a point whose records the retraction of a fused trial step left in Rq; any other point
   // is read as it is given (72-byte rows): Rq is not written here, nor anything else a bound Jacobian reads
@@ -1700,7 +1587,7 @@ int mi_so3n_residual(mi_so3n *q, const mi_vec *R, mi_vec *F, double *sqnorm) {
     KScope ks(ctx, MI_K_SO3_RESIDUAL);
     DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(gq, GQ,
         hipLaunchKernelGGL((k_so3_residual<SQ, GQ>), dim3(grid), dim3(kNlsBlock), 0, ctx->stream, edge_view(q),
-                           GQ ? (const double *)q->Rq : (const double *)R->d, F->d, ctx->partials2)));
+                           GQ ? (const double *)q->Rq.get() : (const double *)R->d, F->d, ctx->partials2)));
   }
   MI_HIP(hipGetLastError());
   if (sqnorm) {
@@ -1715,27 +1602,14 @@ int mi_so3n_jacobian(mi_so3n *q, const mi_vec *R, mi_op **dF, mi_op **dFt) {
   MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
   MI_REQUIRE(q->E > 0, "mi_so3n_jacobian: the problem has no edges (a 3N -> 0 operator)");
   mi_ctx *ctx = q->ctx;
-  MI_TRY(nls_upload(q, true));
+  MI_TRY(ensure_nls(q, true));
   // the linearisation's own copy of the rotations: TNLS evaluates F at trial points while LSQR still uses these operators
   q->jac_quat = q->Rq && q->rq.is(R);
-  if (q->jac_quat) MI_HIP(hipMemcpyAsync(q->Jrot, q->Rq, q->N * 4 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  else MI_HIP(hipMemcpyAsync(q->Jrot, R->d, q->N * 9 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  q->dF = mi_op();
-  q->dF.ctx = ctx;
-  q->dF.n = 3 * q->N;
-  q->dF.n_out = 9 * q->E;
-  q->dF.apply = so3_jac_apply;
-  q->dF.apply_sub_scaled = so3_jac_sub_scaled;
-  q->dF.impl = q;
-  q->dF.borrowed = true;
-  q->dFt = mi_op();
-  q->dFt.ctx = ctx;
-  q->dFt.n = 9 * q->E;
-  q->dFt.n_out = 3 * q->N;
-  q->dFt.apply = so3_jact_apply;
-  q->dFt.apply_sub_scaled = so3_jact_sub_scaled;
-  q->dFt.impl = q;
-  q->dFt.borrowed = true;
+  const size_t words = q->jac_quat ? 4 : 9;
+  MI_HIP(hipMemcpyAsync(q->Jrot.get(), q->jac_quat ? q->Rq.get() : R->d, q->N * words * sizeof(double), hipMemcpyDeviceToDevice,
+                        ctx->stream));
+  q->dF = borrowed_op(ctx, 3 * q->N, 9 * q->E, so3_jac_apply, so3_jac_sub_scaled, q);
+  q->dFt = borrowed_op(ctx, 9 * q->E, 3 * q->N, so3_jact_apply, so3_jact_sub_scaled, q);
   *dF = &q->dF;
   *dFt = &q->dFt;
   return MI_OK;
@@ -1744,25 +1618,8 @@ int mi_so3n_jacobian(mi_so3n *q, const mi_vec *R, mi_op **dF, mi_op **dFt) {
 int mi_so3n_gn_scaling(mi_so3n *q, mi_op **M) {
   SO3_REQUIRE_ARGS(q && M);
   MI_REQUIRE(q->w_nonneg, "the Gauss-Newton scaling 1 / sqrt(2 degw) needs weights >= 0");
-  if (!q->gn_op) {
-    MI_TRY(mi_vec_create(q->ctx, 3 * q->N, &q->gn_diag));
-    if (q->w_cur) {
-      // after a reweighting: from the weights in force, by the pass that keeps it current (winc is rewritten to itself)
-      touch(q->gn_diag);
-      MI_TRY(launch_inc_reweight(q));
-    } else {
-      std::vector<double> degw(q->N, 0.0), d(3 * q->N);
-      for (size_t e = 0; e < q->E; ++e) {
-        degw[(size_t)q->h_ij[2 * e]] += q->h_w[e];
-        degw[(size_t)q->h_ij[2 * e + 1]] += q->h_w[e];
-      }
-      for (size_t i = 0; i < q->N; ++i) d[3 * i] = d[3 * i + 1] = d[3 * i + 2] = degw[i] > 0 ? 1.0 / std::sqrt(2 * degw[i]) : 1.0;
-      MI_TRY(mi_vec_upload(q->gn_diag, d.data(), d.size()));
-    }
-    MI_TRY(mi_op_create_diag(q->ctx, q->gn_diag, &q->gn_op));
-    q->gn_op->borrowed = true;
-  }
-  *M = q->gn_op;
+  MI_TRY(ensure_gn_scaling(q));
+  *M = q->gn_op.get();
   return MI_OK;
 }
 
@@ -1776,33 +1633,26 @@ int mi_so3n_reweight(mi_so3n *q, const mi_vec *R, int kind, double c, double inf
   MI_REQUIRE(!R || (R->ctx == q->ctx && R->n == 9 * q->N), "R must hold N row-major 3x3 blocks");
   MI_REQUIRE(!ctx->uniform_grid, "the reweighting of mi_so3n is single-context");
   if (kind == SO3_ROBUST_L2) c = 1.0;
-  // what was worked out with the old weights: the bound model, the speculative trial model, the Armijo gradient (the rq
-  // key describes a point, not the weights, and stays)
-  q->R = nullptr;
-  q->R_serial = 0;
-  q->trial.clear();
-  q->armijo.clear();
+  invalidate_models(q, true);  // (what was worked out with the old weights)
   if (q->E == 0) {
     if (info) info[0] = info[1] = info[2] = 0.0;
     return MI_OK;
   }
-  if (!q->w_cur) {  // first use: the one-time uploads (sync)
-    MI_TRY(edge_upload(q));
-    MI_TRY(slot_upload(q));
-    MI_TRY(upload((void **)&q->w0, q->h_w.data(), q->E * sizeof(double)));
-    MI_HIP(hipMalloc((void **)&q->w_cur, q->E * sizeof(double)));
-  }
+  // first use: the one-time uploads (sync)
+  MI_TRY(ensure_edge_streams(q));
+  MI_TRY(ensure_slot_words(q));
+  MI_TRY(ensure_weights(q));
   const int grid = edge_grid(q);
   {
     KScope ks(ctx, MI_K_SO3_EDGE_WEIGHT);
     DISPATCH_FLAG(q->sinc_quat, SQ,
         hipLaunchKernelGGL((k_so3_edge_weight<SQ>), dim3(grid), dim3(kNlsBlock), 0, ctx->stream, edge_view(q),
-                           (const double *)q->w0, R ? (const double *)R->d : (const double *)nullptr, kind, c, q->w_cur,
-                           q->swe, ctx->partials2));
+                           (const double *)q->w0.get(), R ? (const double *)R->d : (const double *)nullptr, kind, c,
+                           q->w_cur.get(), q->swe.get(), ctx->partials2));
   }
   MI_HIP(hipGetLastError());
-  if (q->gn_diag) touch(q->gn_diag);
-  MI_TRY(launch_inc_reweight(q));
+  touch(q->gn_diag.get());
+  MI_TRY(launch_inc_reweight(q, q->gn_diag ? q->gn_diag->d : nullptr));
   if (info) {
     MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, grid, 3, ctx->scalars + SLOT_MISC));
     MI_TRY(read_slots_sync(ctx, SLOT_MISC, 3, info));  // the one read-back
@@ -1818,7 +1668,7 @@ int mi_so3n_weights(mi_so3n *q, double *w_host) {
     return MI_OK;
   }
   MI_TRY(stream_wait(q->ctx, "mi_so3n_weights"));
-  MI_HIP(hipMemcpy(w_host, q->w_cur, q->E * sizeof(double), hipMemcpyDeviceToHost));
+  MI_HIP(hipMemcpy(w_host, q->w_cur.get(), q->E * sizeof(double), hipMemcpyDeviceToHost));
   return MI_OK;
 }
 
@@ -1827,21 +1677,16 @@ int mi_so3n_weights(mi_so3n *q, double *w_host) {
 
 namespace {
 
-// quantity `which` (0 objective sum, 1 |Q - Q'|^2, 2 tr C) of k_so3_cert_diag's partial rows -> one sum in *slot, reduced
-// as model_objective_to_slot reduces the objective (which == 0: that very function)
-int cert_rows_to_slot(mi_so3n *q, int grid, int which, double *slot) {
-  mi_ctx *ctx = q->ctx;
-  if (which == 0) return model_objective_to_slot(q, grid, slot);
-  const double *rows = ctx->partials2 + (size_t)which * kCertComps * kMaxRows;
-  const int comps = (grid + kMaxRows - 1) / kMaxRows;
-  if (comps == 1) return reduce_rows_allreduce(ctx, rows, grid, 1, slot);
-  double *tmp = ctx->scalars + SLOT_RAW + which * kCertComps;
-  MI_TRY(reduce_rows_allreduce(ctx, rows, kMaxRows, comps, tmp));
-  hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(1), 0, ctx->stream, (const double *)tmp, comps, slot);
-  MI_HIP(hipGetLastError());
+// q->cert / q->lap: Esl, written by k_so3_cert_diag / k_so3_lap_diag, read by k_so3_cert_panel (k_so3_lap_jacobi); Y
+int ensure_cert_slot(mi_so3n *q, Owned<mi_so3n_cert> &slot, bool with_Y) {
+  if (slot) return MI_OK;
+  Owned<mi_so3n_cert> c(new mi_so3n_cert());
+  c->q = q;
+  MI_TRY(dev_alloc(c->Esl, q->nslices * 6 * 64));
+  if (with_Y) MI_TRY(vec_alloc(q->ctx, 9 * q->N, c->Y));
+  slot = std::move(c);
   return MI_OK;
 }
-
 int cert_launch(const mi_so3n_cert *c, const CertCols &X, int k, double *Z) {
   const mi_so3n *q = c->q;
   mi_ctx *ctx = q->ctx;
@@ -1850,7 +1695,7 @@ int cert_launch(const mi_so3n_cert *c, const CertCols &X, int k, double *Z) {
 #define CERT_PANEL(KCV)                                                                                                     \
   DISPATCH_FLAG(q->sinc_quat, SQ,                                                                                           \
                 hipLaunchKernelGGL((k_so3_cert_panel<KCV, SQ>), grid, dim3(256), 0, ctx->stream, view(q),                   \
-                                   (const double *)q->Sinc, (const double *)q->winc, (const double *)c->Esl, X, k, Z))
+                                   (const double *)q->Sinc.get(), (const double *)q->winc.get(), (const double *)c->Esl.get(), X, k, Z))
   if (KCsel == 1) { CERT_PANEL(1); }
   else if (KCsel == 4) { CERT_PANEL(4); }
   else { CERT_PANEL(8); }
@@ -1859,13 +1704,16 @@ int cert_launch(const mi_so3n_cert *c, const CertCols &X, int k, double *Z) {
   return MI_OK;
 }
 constexpr int kCertMaxK = 96;  // the widest panel of the LOBPCG building blocks (lobpcg.hip: kGramMaxK)
-// Z (3N x k) against an input block of `cols` columns: both in the certificate's context, large enough, not overlapping
-int cert_check_io(const mi_so3n_cert *c, const mi_vec *X, int cols, const mi_vec *Z, int k) {
-  const size_t m = 3 * c->q->N;
-  MI_REQUIRE(X->ctx == c->q->ctx && Z->ctx == c->q->ctx, "panel belongs to another context");
+// Z (3N x k) against an input block of `cols` columns: both in the problem's context, large enough, not overlapping
+// (same_ok: or one and the same panel)
+int cert_check_io(const mi_so3n *q, const mi_vec *X, int cols, const mi_vec *Z, int k, bool same_ok = false) {
+  const size_t m = 3 * q->N;
+  MI_REQUIRE(X->ctx == q->ctx && Z->ctx == q->ctx, "panel belongs to another context");
   MI_REQUIRE(X->n >= m * (size_t)cols, "X holds %zu doubles, needs 3N * k = %zu * %d", X->n, m, cols);
   MI_REQUIRE(Z->n >= m * (size_t)k, "Z holds %zu doubles, needs 3N * k = %zu * %d", Z->n, m, k);
-  MI_REQUIRE(Z->d + m * (size_t)k <= X->d || X->d + m * (size_t)cols <= Z->d, "input and output panels must not overlap");
+  const bool apart = Z->d + m * (size_t)k <= X->d || X->d + m * (size_t)cols <= Z->d;
+  if (same_ok) MI_REQUIRE(Z->d == X->d || apart, "input and output panels must be the same or not overlap");
+  else MI_REQUIRE(apart, "input and output panels must not overlap");
   return MI_OK;
 }
 
@@ -1878,29 +1726,20 @@ int mi_so3n_certificate(mi_so3n *q, const mi_vec *R, mi_so3n_cert **out, double 
   MI_REQUIRE(R->ctx == q->ctx && R->n == 9 * q->N, "R must hold N row-major 3x3 blocks");
   mi_ctx *ctx = q->ctx;
   MI_REQUIRE(!ctx->uniform_grid, "the certificate of mi_so3n is single-context");
-  if (!q->cert) {
-    mi_so3n_cert *c = new mi_so3n_cert();
-    c->q = q;
-    q->cert = c;
-    MI_HIP(hipMalloc((void **)&c->Esl, q->nslices * 6 * 64 * sizeof(double)));
-    MI_TRY(mi_vec_create(ctx, 9 * q->N, &c->Y));
-  }
-  mi_so3n_cert *c = q->cert;
-  touch(c->Y);
+  MI_TRY(ensure_cert_slot(q, q->cert, true));
+  mi_so3n_cert *c = q->cert.get();
+  touch(c->Y.get());
   // the neighbours gathered as mi_so3n_objective gathers them (quaternion records when the problem keeps them: those the
   // retraction of a fused trial step left for this very point, else converted here first)
-  const bool gq = q->Rq != nullptr, have_quat = gq && q->rq.is(R);
-  if (gq && !have_quat) {
-    q->rq.clear();
-    hipLaunchKernelGGL(k_so3_quat, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, (const double *)R->d, q->Rq);
-  }
+  const bool gq = q->Rq != nullptr;
+  ensure_rq(q, R->d, q->rq.is(R));
   const int grid = model_grid(q);
   DISPATCH_FLAG(q->sinc_quat, SQ, DISPATCH_FLAG(gq, GQ,
       hipLaunchKernelGGL((k_so3_cert_diag<SQ, GQ>), dim3(grid), dim3(256), 0, ctx->stream, view(q), (const double *)R->d,
-                         (const double *)q->Rq, (const double *)q->Sinc, (const double *)q->winc, c->Esl, c->Y->d,
-                         ctx->partials2)));
+                         (const double *)q->Rq.get(), (const double *)q->Sinc.get(), (const double *)q->winc.get(), c->Esl.get(),
+                         c->Y->d, ctx->partials2)));
   MI_HIP(hipGetLastError());
-  for (int which = 0; which < 3; ++which) MI_TRY(cert_rows_to_slot(q, grid, which, ctx->scalars + SLOT_MISC + which));
+  for (int which = 0; which < 3; ++which) MI_TRY(partial_rows_to_slot(q, grid, which, ctx->scalars + SLOT_MISC + which));
   double buf[3];
   MI_TRY(read_slots_sync(ctx, SLOT_MISC, 3, buf));  // the one read-back
   info[0] = .25 * buf[0];  // (every edge from both ends)
@@ -1913,7 +1752,7 @@ int mi_so3n_certificate(mi_so3n *q, const mi_vec *R, mi_so3n_cert **out, double 
 int mi_so3n_cert_apply(mi_so3n_cert *c, int k, const mi_vec *X, mi_vec *Z) {
   SO3_REQUIRE_ARGS(c && X && Z);
   MI_REQUIRE(k >= 1 && k <= kCertMaxK, "panel width must be in [1,%d]", kCertMaxK);
-  MI_TRY(cert_check_io(c, X, k, Z, k));
+  MI_TRY(cert_check_io(c->q, X, k, Z, k));
   touch(Z);
   return cert_launch(c, CertCols{{X->d, X->d, X->d}, k, k}, k, Z->d);
 }
@@ -1927,7 +1766,7 @@ int mi_so3n_cert_apply_blocks(mi_so3n_cert *c, const mi_panel_blocks *X, mi_vec 
     k += X->cols[b];
   }
   MI_REQUIRE(k <= kCertMaxK, "panel width must be in [1,%d]", kCertMaxK);
-  for (int b = 0; b < X->nblocks; ++b) MI_TRY(cert_check_io(c, X->block[b], X->cols[b], Z, k));
+  for (int b = 0; b < X->nblocks; ++b) MI_TRY(cert_check_io(c->q, X->block[b], X->cols[b], Z, k));
   const double *b0 = X->block[0]->d, *b1 = X->nblocks > 1 ? X->block[1]->d : b0, *b2 = X->nblocks > 2 ? X->block[2]->d : b1;
   const int n0 = X->nblocks > 1 ? X->cols[0] : k, n01 = X->nblocks > 2 ? n0 + X->cols[1] : k;
   touch(Z);
@@ -1937,7 +1776,7 @@ int mi_so3n_cert_apply_blocks(mi_so3n_cert *c, const mi_panel_blocks *X, mi_vec 
 int mi_so3n_cert_null_panel(mi_so3n_cert *c, mi_vec **Y) {
   SO3_REQUIRE_ARGS(c && Y);
   MI_REQUIRE(c->Y, "the connection Laplacian of mi_so3n_laplacian has no panel Y");
-  *Y = c->Y;
+  *Y = c->Y.get();
   return MI_OK;
 }
 
@@ -1950,29 +1789,26 @@ namespace {
 int lap_refresh(mi_so3n *q) {
   mi_ctx *ctx = q->ctx;
   MI_REQUIRE(!ctx->uniform_grid, "the connection Laplacian of mi_so3n is single-context");
-  if (!q->lap) {
-    mi_so3n_cert *c = new mi_so3n_cert();
-    c->q = q;
-    q->lap = c;
-    MI_HIP(hipMalloc((void **)&c->Esl, q->nslices * 6 * 64 * sizeof(double)));
-  }
-  hipLaunchKernelGGL(k_so3_lap_diag, dim3(node_grid(q)), dim3(256), 0, ctx->stream, view(q), (const double *)q->winc,
-                     q->lap->Esl);
+  MI_TRY(ensure_cert_slot(q, q->lap, false));
+  hipLaunchKernelGGL(k_so3_lap_diag, dim3(node_grid(q)), dim3(256), 0, ctx->stream, view(q), (const double *)q->winc.get(),
+                     q->lap->Esl.get());
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
+// round_words (RW_WORDS): what k_so3_round_sign / k_so3_round count and mi_so3n_round / mi_so3n_project read back
+int ensure_round_words(mi_so3n *q) { return q->round_words ? MI_OK : dev_alloc(q->round_words, RW_WORDS); }
 // the count words of one rounding call, zeroed (RW_EXTREME: the neutral element of the call's min or max)
 int round_words_init(mi_so3n *q, double extreme) {
-  if (!q->round_words) MI_HIP(hipMalloc((void **)&q->round_words, RW_WORDS * sizeof(unsigned long long)));
+  MI_TRY(ensure_round_words(q));
   unsigned long long bits;
   std::memcpy(&bits, &extreme, sizeof(bits));
-  hipLaunchKernelGGL(k_so3_round_init, dim3(1), dim3(1), 0, q->ctx->stream, q->round_words, bits);
+  hipLaunchKernelGGL(k_so3_round_init, dim3(1), dim3(1), 0, q->ctx->stream, q->round_words.get(), bits);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
 int round_words_read(mi_so3n *q, const char *what, unsigned long long words[RW_WORDS]) {
   MI_TRY(stream_wait(q->ctx, what));
-  MI_HIP(hipMemcpy(words, q->round_words, RW_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  MI_HIP(hipMemcpy(words, q->round_words.get(), RW_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return MI_OK;
 }
 double word_as_double(unsigned long long w) {
@@ -1988,22 +1824,17 @@ extern "C" {
 int mi_so3n_laplacian(mi_so3n *q, mi_so3n_cert **out) {
   SO3_REQUIRE_ARGS(q && out);
   MI_TRY(lap_refresh(q));
-  *out = q->lap;
+  *out = q->lap.get();
   return MI_OK;
 }
 
 int mi_so3n_lap_jacobi(mi_so3n *q, int k, const mi_vec *X, mi_vec *Z) {
   SO3_REQUIRE_ARGS(q && X && Z);
   MI_REQUIRE(k >= 1 && k <= kCertMaxK, "panel width must be in [1,%d]", kCertMaxK);
-  const size_t m = 3 * q->N;
-  MI_REQUIRE(X->ctx == q->ctx && Z->ctx == q->ctx, "panel belongs to another context");
-  MI_REQUIRE(X->n >= m * (size_t)k, "X holds %zu doubles, needs 3N * k = %zu * %d", X->n, m, k);
-  MI_REQUIRE(Z->n >= m * (size_t)k, "Z holds %zu doubles, needs 3N * k = %zu * %d", Z->n, m, k);
-  MI_REQUIRE(Z->d == X->d || Z->d + m * (size_t)k <= X->d || X->d + m * (size_t)k <= Z->d,
-             "input and output panels must be the same or not overlap");
+  MI_TRY(cert_check_io(q, X, k, Z, k, /*same_ok=*/true));
   if (!q->lap) MI_TRY(lap_refresh(q));  // (else: the diagonal of the latest mi_so3n_laplacian call)
   touch(Z);
-  hipLaunchKernelGGL(k_so3_lap_jacobi, dim3(node_grid(q)), dim3(256), 0, q->ctx->stream, view(q), (const double *)q->lap->Esl,
+  hipLaunchKernelGGL(k_so3_lap_jacobi, dim3(node_grid(q)), dim3(256), 0, q->ctx->stream, view(q), (const double *)q->lap->Esl.get(),
                      k, (const double *)X->d, Z->d);
   MI_HIP(hipGetLastError());
   return MI_OK;
@@ -2019,9 +1850,9 @@ int mi_so3n_round(mi_so3n *q, const mi_vec *V, mi_vec *R, double info[4]) {
   MI_TRY(round_words_init(q, HUGE_VAL));
   touch(R);
   const int grid = grid_for(ctx, q->N, 1);
-  hipLaunchKernelGGL(k_so3_round_sign, dim3(grid), dim3(256), 0, ctx->stream, q->N, (const double *)V->d, q->round_words);
+  hipLaunchKernelGGL(k_so3_round_sign, dim3(grid), dim3(256), 0, ctx->stream, q->N, (const double *)V->d, q->round_words.get());
   hipLaunchKernelGGL(k_so3_round<true>, dim3(grid), dim3(256), 0, ctx->stream, q->N, (const double *)V->d, R->d,
-                     q->round_words);
+                     q->round_words.get());
   MI_HIP(hipGetLastError());
   if (info) {
     unsigned long long w[RW_WORDS];
@@ -2044,7 +1875,7 @@ int mi_so3n_project(mi_so3n *q, const mi_vec *M, mi_vec *R, double info[3]) {
   MI_TRY(round_words_init(q, 0.0));
   touch(R);
   hipLaunchKernelGGL(k_so3_round<false>, dim3(grid_for(ctx, q->N, 1)), dim3(256), 0, ctx->stream, q->N, (const double *)M->d,
-                     R->d, q->round_words);
+                     R->d, q->round_words.get());
   MI_HIP(hipGetLastError());
   if (info) {
     unsigned long long w[RW_WORDS];

@@ -144,12 +144,6 @@ __global__ __launch_bounds__(kBlock) void k_spmv_sub_scaled(SellView A, const do
   block_partials_store<1>(a, lds, partials);
 }
 
-int upload(void **dst, const void *src, size_t bytes) {
-  MI_HIP(hipMalloc(dst, bytes ? bytes : 8));
-  if (bytes) MI_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return MI_OK;
-}
-
 // The same on the lean pipelined core (packed matrix when there is one)
 template <bool HALO, bool PK>
 __global__ __launch_bounds__(kBlock) void k_spmv_sub_scaled_stream(SellView A, const double *__restrict__ V,

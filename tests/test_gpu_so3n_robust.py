@@ -168,6 +168,81 @@ def test_no_stale_model_after_a_reweighting(ctx, name):
     print(name, "first use after a reweighting, largest error in units of eps:", _compare(a, b, name))
 
 
+def _first_use_problem():
+    """N = 70: two slices, the second with 6 live lanes and 58 padding lanes; a ring over every node but one (isolated),
+    60 chords, one zero-weight edge; noisy rotation measurements, weights in [0.5, 2]; a point off the truth"""
+    from types import SimpleNamespace
+    N, iso = 70, 33
+    rng = np.random.Generator(np.random.PCG64(70))
+
+    def rot(v):
+        t = np.linalg.norm(v, axis=-1)[..., None, None]
+        K = np.zeros(v.shape[:-1] + (3, 3))
+        K[..., 0, 1], K[..., 0, 2], K[..., 1, 2] = -v[..., 2], v[..., 1], -v[..., 0]
+        K = K - np.swapaxes(K, -1, -2)
+        return np.eye(3) + np.sin(t) / t * K + (1 - np.cos(t)) / t ** 2 * (K @ K)
+
+    nodes = np.array([i for i in range(N) if i != iso])
+    a, b = rng.integers(0, N - 1, size=60), rng.integers(0, N - 1, size=60)
+    b = np.where(a == b, (b + 1) % (N - 1), b)
+    ei = np.concatenate([nodes, nodes[a]]).astype(np.int32)
+    ej = np.concatenate([np.roll(nodes, -1), nodes[b]]).astype(np.int32)
+    truth = rot(rng.normal(size=(N, 3)))
+    Rt = np.swapaxes(truth[ei], 1, 2) @ truth[ej] @ rot(0.05 * rng.normal(size=(ei.size, 3)))
+    w = rng.uniform(0.5, 2.0, size=ei.size)
+    w[17] = 0.0
+    R = truth @ rot(0.2 * rng.normal(size=(N, 3)))
+    return SimpleNamespace(N=N, ei=ei, ej=ej, Rt=Rt.reshape(-1, 9), w=w, R=R)
+
+
+def _views(ctx, prob, c, R):
+    """(exact, close) as _compare takes them: f and the gradient of a fresh model; F, dF x, dF* y, the scaling of ones"""
+    rng = np.random.Generator(np.random.PCG64(71))
+    x, y = rng.normal(size=3 * c.N), rng.normal(size=9 * c.ei.size)
+    close = {"residual": (prob.residual(R).numpy(), 9)}
+    dF, dFt = prob.jacobian(R)
+    close["dF"] = (dF.apply(ctx.upload(x)).numpy(), 9)
+    close["dFt"] = (dFt.apply(ctx.upload(y)).numpy(), 3)
+    close["gn_scaling"] = (prob.gn_scaling().apply(ctx.upload(np.ones(3 * c.N))).numpy(), 3)
+    exact = {"objective": np.array([prob.objective(R)]), "gradient": prob.model(R)[0].numpy()}
+    return exact, close
+
+
+def test_first_use_order_does_not_change_a_reweighted_problem(ctx):
+    """The rule behind (d): whichever of the least-squares views, the scaling and the reweighting is asked for first, the
+    views are those of the weights in force.  A: reweight -> residual -> jacobian -> gn_scaling; B: gn_scaling -> jacobian
+    -> residual -> reweight at the same point, then the views again; C: a fresh problem with A's weights.
+    A against B bit for bit: both orders end in the same kernels on the same device weights (so it was before the
+    first-use paths became one function per resource: the commit before gives equal bits in every quantity).  Against C
+    the bar of (b): the host and the device sum degw in different orders.  The reweighting waits for the host as often in
+    either order (never without info)."""
+    c = _first_use_problem()
+    R = ctx.upload(c.R.ravel())
+    A = _problem(ctx, c)
+    n0 = ctx.sync_count()
+    A.reweight(R, "cauchy", 0.5, info=False)
+    syncs_a = ctx.sync_count() - n0
+    va = _views(ctx, A, c, R)
+    B = _problem(ctx, c)
+    B.gn_scaling()
+    B.jacobian(R)
+    B.residual(R)
+    n0 = ctx.sync_count()
+    B.reweight(R, "cauchy", 0.5, info=False)
+    syncs_b = ctx.sync_count() - n0
+    vb = _views(ctx, B, c, R)
+    print("host waits of the reweighting call: first use", syncs_a, "everything there", syncs_b)
+    assert syncs_a == 0 and syncs_b == 0
+    w = A.weights()
+    assert np.array_equal(w, B.weights()) and w[17] == 0.0 and not np.array_equal(w, c.w)
+    _compare(va, vb, "A against B", bitwise_close=True)
+    Cp = _problem(ctx, c, w)
+    vc = _views(ctx, Cp, c, R)
+    print("against a fresh problem, largest error in units of eps:", _compare(va, vc, "A against C"), _compare(vb, vc, "B against C"))
+    info = A.info()
+    assert info["nslices"] == 2 and info["nnzb"] == 2 * c.ei.size
+
+
 def test_no_host_wait_without_info(ctx):
     """(f)"""
     c = rr.variant("ring_chords_1500:outliers")
