@@ -25,7 +25,7 @@ CFLAGS = [
     "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
     "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-I", os.path.join(HERE, "include"), "-I", "/opt/rocm/include",
 ]
-CFLAGS += os.environ.get("MI355OPT_EXTRA_CFLAGS", "").split()  # experiments (e.g. -DMI_SPMM_CHUNK=8)
+CFLAGS += os.environ.get("MI355OPT_EXTRA_CFLAGS", "").split()  # experiment builds (e.g. -DMI_WIN_STAMPS)
 LDFLAGS = ["-shared", "-L/opt/rocm/lib", "-lrccl", "-ldl", "-Wl,-rpath,/opt/rocm/lib", "-Wl,--no-undefined"]
 
 

@@ -365,9 +365,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 // is decided once, in the pointer set-up).  Every product is the product the separate tiles form: same bits.
 // PAIR = false: S'T alone (upper block triangle) -- the generalized problem forms S'A(S) and S'B(S) with two launches
 // of it (r05); T as column blocks like S, so [AX | A(W) | A(P)] need not be assembled either.
-#ifndef MI_GRAM_DEEP
-#define MI_GRAM_DEEP 1
-#endif
 template <int T, bool HALF, bool PAIR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, (PAIR ? T >= 4 : T >= 5) ? 1 : 2))) void k_gram_pair_sym(
     size_t mfull, size_t m, int k, ColBlocks S, ColBlocks Tb, double *__restrict__ partialA,
@@ -404,7 +401,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, (PAIR ? 
   // DEEP (r05): the operands of TWO steps ahead are in flight (fa / fb).  One step's MFMA block -- 100 MFMAs at T = 5 with
   // the shared last column, ~1.5 us -- is shorter than a loaded memory round trip, so with one step of look-ahead the
   // wave waits for memory every step and the MFMAs the shared column saves buy nothing (measured: 527 us either way).
-  constexpr bool DEEP = MI_GRAM_DEEP && PAIR && T >= 4;
+  constexpr bool DEEP = PAIR && T >= 4;
   double4l fa[DEEP ? T : 1], fb[DEEP ? T : 1];
   size_t r0 = rowwave * 16;
   auto fetch = [&](double4l(&va)[DEEP ? T : T], double4l(&vb)[DEEP ? T : T], size_t r) {
@@ -929,24 +926,11 @@ __global__ __launch_bounds__(kWinBlock) void k_spmm_colmajor_win(SellView A, Win
       for (int j = 0; j < kFarCap; ++j) f[j] = pinned_load(reinterpret_cast<const unsigned *>(fb + j * 256));
     }
   };
-  // (MI_SPMM_ABLATE_FAR: timing-only experiment builds, WRONG results -- what the two far gathers of a row cost.
-  //  1: they read rows next to the wave's own chunk instead (same instructions, lines that are in L1 / L2 anyway: the
-  //     time of the pass if the far rows cost no traffic beyond the L2); 2: no far loads at all.  r06, EXPERIMENTS.md)
   auto far_rows = [&](const unsigned (&f)[kFarCap], double (&g)[kFarCap][KC]) {
 #pragma unroll
     for (int s_ = 0; s_ < kFarCap; ++s_)
 #pragma unroll
-      for (int c = 0; c < KC; ++c) {
-#if defined(MI_SPMM_ABLATE_FAR) && MI_SPMM_ABLATE_FAR == 2
-        g[s_][c] = (double)f[s_];
-#elif defined(MI_SPMM_ABLATE_FAR) && MI_SPMM_ABLATE_FAR == 1
-        // f[0] = row + D, f[1] = row - D (load_far): back to the row itself, one / two chunks further on
-        const unsigned near_ = (s_ == 0 ? f[0] - W.far_d : f[1] + W.far_d) + 64u * (unsigned)(s_ + 1);
-        g[s_][c] = pinned_load(xc[c] + (near_ < (unsigned)m ? near_ : 0u));
-#else
-        g[s_][c] = pinned_load(xc[c] + f[s_]);
-#endif
-      }
+      for (int c = 0; c < KC; ++c) g[s_][c] = pinned_load(xc[c] + f[s_]);
   };
 
   int slice = t0 * NW + w;
@@ -1106,17 +1090,11 @@ __global__ __launch_bounds__(kWinBlock) void k_spmm_colmajor_win(SellView A, Win
 // thread, prefetched a step ahead; the neighbouring tiles' workgroups are in the same z-range on the same XCD).
 // 1.5 loads per output element.  Entries are decoded from the packed words (mi_csr::pk: (col - row) << 8 | value index)
 // in storage order with the same fused multiply-adds as k_spmm_colmajor_pk: the same bits.
-// (waves x row groups per wave: 4 x 2 -- 230-245 VGPRs, two workgroups = 8 waves per CU, 496-514 us at cfg5 -- or, with
-// -DMI_SWEEP_WAVES=8, 8 x 1: the same tile and window, 128 VGPRs, 16 waves per CU: 518-521 us.  Twice the occupancy
-// changes nothing: with every workgroup's step requested in one burst the pass is paced by the memory system serving
-// 512 workgroups x 96 KB per round, at 4.3-4.5 TB/s)
+// (4 waves x 2 row groups per wave, two workgroups per CU; 8 x 1 was no faster: EXPERIMENTS.md "Decided knobs")
 constexpr int kSwRows = 512, kSwHalo = 128, kSwWin = kSwRows + 2 * kSwHalo;
-#ifndef MI_SWEEP_WAVES
-#define MI_SWEEP_WAVES 4
-#endif
-constexpr int kSwWaves = MI_SWEEP_WAVES, kSwBlock = 64 * kSwWaves, kSwGroups = kSwRows / 64 / kSwWaves;
+constexpr int kSwWaves = 4, kSwBlock = 64 * kSwWaves, kSwGroups = kSwRows / 64 / kSwWaves;
 template <int KC, int HW, bool RES>
-__global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(kSwWaves == 8 ? 4 : 2, kSwWaves == 8 ? 4 : 2))) void k_spmm_colmajor_sweep(SellView A, unsigned D, int tiles, int zs, int k,
+__global__ __launch_bounds__(kSwBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_spmm_colmajor_sweep(SellView A, unsigned D, int tiles, int zs, int k,
                                                                    int c_first, ColBlocks X, double *__restrict__ Y,
                                                                    ThetaArg theta, double *__restrict__ R,
                                                                    double *__restrict__ partials_all) {

@@ -31,9 +31,7 @@ __device__ __forceinline__ long long slice_bound(const long long *sp, size_t i) 
 typedef __attribute__((address_space(4))) const int ConstInt;
 __device__ __forceinline__ int scalar_int(const int *p, size_t i) { return ((ConstInt *)p)[i]; }
 
-#ifndef MI_SPMM_CHUNK
-#define MI_SPMM_CHUNK 4  // measured on cfg2: 4 -> 33.4 us, 8 -> 34.1 us, entry-at-a-time -> 35 us
-#endif
+constexpr int kSpmmChunk = 4;  // entries per chunk of the gather loops (EXPERIMENTS.md "Decided knobs")
 constexpr int kSlicesPerGroup = kWaves;  // one workgroup pass covers 16 slices = 1024 rows
 
 // acc[0..P) = row `row` of A times V.  One lane per row; a wave owns one slice, so the loads of
@@ -44,12 +42,12 @@ __device__ __forceinline__ void sell_row_times(const SellView &A, size_t slice, 
   const long long b0 = A.slice_ptr[slice], b1 = A.slice_ptr[slice + 1];
 #pragma unroll
   for (int c = 0; c < P; ++c) acc[c] = 0;
-  // Chunks of MI_SPMM_CHUNK entries: all (value, column) pairs of a chunk are loaded first, then the
+  // Chunks of kSpmmChunk entries: all (value, column) pairs of a chunk are loaded first, then the
   // CH x P gathers are issued back to back (memory-level parallelism instead of a load -> gather
   // dependency per entry).  Entries beyond the slice width are predicated off by a select.
   // (Non-temporal loads of the matrix stream were measured SLOWER, 40 vs 33 us: the 87 MB matrix is
   // Infinity-Cache resident across iterations and `nt` forfeits that.)
-  constexpr int CH = MI_SPMM_CHUNK;
+  constexpr int CH = kSpmmChunk;
   for (long long k = b0; k < b1; k += CH) {
     double a[CH];
     size_t cidx[CH];
@@ -63,11 +61,7 @@ __device__ __forceinline__ void sell_row_times(const SellView &A, size_t slice, 
     }
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
-#ifdef MI_DEBUG_NO_GATHER  // timing experiment only: every entry reads the lane's own row
-      const double *src = V + (slice * 64 + lane < A.n ? slice * 64 + lane : 0) * P + 0 * cidx[j];
-#else
       const double *src = (cidx[j] < A.n) ? (V + cidx[j] * P) : (A.halo + (cidx[j] - A.n) * P);
-#endif
 #pragma unroll
       for (int c = 0; c < P; ++c) {
         const double t = a[j] * src[c];
@@ -99,7 +93,7 @@ __device__ __forceinline__ void sell_row_times(const SellView &A, size_t slice, 
 // NW: the waves of the workgroup (the wave takes every NW-th slice of [first, end)).
 // CHK: entries per chunk (rows of 8 doubles gather 64 bytes per entry: two of them in flight per lane keep the
 // register cost of a chunk what four 24-byte gathers cost).
-template <int P, bool HALO, bool PK, class Epi, int NW = kWaves, int CHK = MI_SPMM_CHUNK>
+template <int P, bool HALO, bool PK, class Epi, int NW = kWaves, int CHK = kSpmmChunk>
 __device__ __forceinline__ void sell_stream(const SellView &A, size_t first, size_t end, int lane,
                                             const double *__restrict__ V, const double *vt, Epi &epi) {
   constexpr int CH = CHK;
@@ -168,9 +162,6 @@ __device__ __forceinline__ void sell_stream(const SellView &A, size_t first, siz
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
       const char *base = reinterpret_cast<const char *>(V);
-#ifdef MI_ABLATE_GATHER_OWN  // (timing experiment only: every entry reads the lane's own row -- wrong results)
-      ci[j] = (unsigned)(slice * 64) + (unsigned)lane < nloc ? (unsigned)(slice * 64) + (unsigned)lane : 0u;
-#endif
       unsigned boff = ci[j] * (unsigned)(P * 8);
       if (HALO && ci[j] >= nloc) {
         base = reinterpret_cast<const char *>(A.halo);
@@ -421,10 +412,7 @@ constexpr int kMaxWinChunks = 4;
 #endif
 constexpr int kFarCap = 2;
 constexpr int kWinHead = 8;
-#ifndef MI_WIN_WAVES
-#define MI_WIN_WAVES 4
-#endif
-constexpr int kWinWaves = MI_WIN_WAVES;  // waves per workgroup of the window kernels = slices per tile
+constexpr int kWinWaves = 4;  // waves per workgroup of the window kernels = slices per tile
 constexpr int kWinBlock = kWinWaves * 64;
 constexpr int kWinRingRowsMax = (2 * kWinWaves + 2 * kMaxWinChunks) * 64;  // ring rows at the widest window
 constexpr int kWinFarRows = kWinWaves * kFarCap * 64;                       // far slots of a workgroup
@@ -464,7 +452,7 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 // 64 consecutive rows of a row-major field as the wave holds them after P coalesced 512-byte loads (lane l: the
-// doubles l, 64 + l, ... of the 64 P): stored as rows RS doubles apart / one lane's row read back
+// doubles l, 64 + l, ... of the 64 P): stored as rows RS doubles apart
 template <int P, int RS>
 __device__ __forceinline__ void image_store(LdsDouble *rows, int lane, const double (&buf)[P]) {
   if constexpr (RS == P) {
@@ -478,23 +466,7 @@ __device__ __forceinline__ void image_store(LdsDouble *rows, int lane, const dou
     }
   }
 }
-template <int P, int RS>
-__device__ __forceinline__ void image_row(const LdsDouble *rows, int lane, double (&out)[P]) {
-  const LdsDouble *l = rows + (unsigned)lane * (unsigned)RS;
-#pragma unroll
-  for (int c = 0; c < P; ++c) out[c] = l[c];
-}
-// An epilogue that declares `using wants_scratch = void;` is handed the wave's far slots (2 x 64 rows, RS doubles apart) as
-// scratch space: end(slice, acc, vrow, scratch) -- free once the slice's entries are done.
-template <class E, class = void>
-struct EpiScratch : std::false_type {};
-template <class E>
-struct EpiScratch<E, std::void_t<typename E::wants_scratch>> : std::true_type {};
 
-#ifndef MI_WIN_FARC
-#define MI_WIN_FARC 1   // pure far structure, one context: far rows as coalesced images (sell_window FARC) -- 1: the wide rows
-                        // (p = 5 / 6 / 7: 46.7 / 57.3 / 78.0 -> 46.3 / 56.1 / 74.8 us), 2: also p <= 4 (no change there)
-#endif
 // the window-form matrix arrays (mi_csr::wk, wfar) and constants
 struct WinView {
   const uint32_t *__restrict__ wk;
@@ -529,13 +501,7 @@ __device__ __forceinline__ void sell_window(const SellView &A, const WinView &W,
   static_assert(!FARC || (FARD && !HALO), "coalesced far rows: pure far structure, one context");
   constexpr int NW = kWinWaves;
   const int nchunks = (int)A.nslices;
-#ifdef MI_WIN_DEBUG  // timing experiments only (wrong results): flags in the high bits of wc
-  const int dbg = W.wc >> 8;
-  const int wc = W.wc & 255, nc = W.nc;
-#else
-  constexpr int dbg = 0;
   const int wc = W.wc, nc = W.nc;
-#endif
   const unsigned nloc = (unsigned)A.n;
   const unsigned nPbytes = (unsigned)(A.n * P * 8);
   const unsigned lane8 = (unsigned)lane * 8u, lane4 = (unsigned)lane * 4u;
@@ -603,10 +569,6 @@ __device__ __forceinline__ void sell_window(const SellView &A, const WinView &W,
       for (int j = 0; j < kFarCap; ++j) f[j] = pinned_load(reinterpret_cast<const unsigned *>(fb + j * 256));
     }
   };
-  auto load_head = [&](Head &h, int kk, int sl) {
-    load_words(h, kk, sl);
-    load_far(h.f, sl);
-  };
   auto far_row = [&](unsigned c, double (&out)[P]) {
     const char *base = reinterpret_cast<const char *>(V);
     unsigned boff = c * (unsigned)(P * 8);
@@ -643,16 +605,12 @@ __device__ __forceinline__ void sell_window(const SellView &A, const WinView &W,
     b1 = (int)slice_bound(A.slice_ptr, slice + 1);
   }
   Head h;
-#ifndef MI_WIN_NO_FARAHEAD
   // Far rows are gathered ONE TILE AHEAD: during a tile the registers gf hold this slice's far rows (gathered while
   // the previous tile ran), h.c its words and h.f the far columns of the NEXT slice.  The entry loop then waits for
   // no memory at all; the tile's only waits are for the staged chunk and for the X/Y rows at its end.
   unsigned f0[kFarCap];
   if constexpr (!FARC) load_far(f0, have ? slice : 0);
   load_words(h, k, have ? slice : 0);
-#else
-  load_head(h, k, have ? slice : 0);
-#endif
   // ring: the first tile's window, the zero row
   int slot_own;  // ring slot of the wave's own chunk (= slice % nc), advanced by 16 per tile
   {
@@ -676,7 +634,6 @@ __device__ __forceinline__ void sell_window(const SellView &A, const WinView &W,
     slot_own = (t0 * NW + w) % nc;
   }
   int slot_job = (t0 * NW + NW + wc + w) % nc;  // slot of the chunk this wave stages during the first tile
-#ifndef MI_WIN_NO_FARAHEAD
   double gf[kFarCap][P];
   {
     const bool more0 = have && t0 + 1 < t1 && slice + NW < nchunks;
@@ -689,7 +646,6 @@ __device__ __forceinline__ void sell_window(const SellView &A, const WinView &W,
       for (int s = 0; s < kFarCap; ++s) far_row(f0[s], gf[s]);
     }
   }
-#endif
   lds_barrier();
   MI_STAMP(1, 0.0);
 
@@ -698,14 +654,13 @@ __device__ __forceinline__ void sell_window(const SellView &A, const WinView &W,
     const int qj = (t + 1) * NW + wc + w;  // staged for tile t + 1 (its last wc chunks included)
     const bool job = t + 1 < t1 && qj < nchunks;
     double pre[P] = {};
-    if (!(dbg & 16)) chunk_load(job ? qj : 0, pre);  // unconditional: the s_waitcnt counts below stay exact on every path
+    chunk_load(job ? qj : 0, pre);  // unconditional: the s_waitcnt counts below stay exact on every path
     if (have) {
       const int nslice = slice + NW;
       const bool more = t + 1 < t1 && nslice < nchunks;
       int q0 = k, q1 = b1;  // nothing follows: the prefetch re-reads this slice
       if (more) { q0 = (int)slice_bound(A.slice_ptr, nslice); q1 = (int)slice_bound(A.slice_ptr, nslice + 1); }
       // ---- this slice's operands become LDS contents and addresses; the registers take the next slice's -------
-#ifndef MI_WIN_NO_FARAHEAD
       unsigned wd[HW];
 #pragma unroll
       for (int j = 0; j < HW; ++j) wd[j] = entry_word(h, j, k, b1);
@@ -724,17 +679,7 @@ __device__ __forceinline__ void sell_window(const SellView &A, const WinView &W,
         const bool more2 = more && t + 2 < t1 && nslice2 < nchunks;
         load_far(h.f, more2 ? nslice2 : (more ? nslice : slice));
       }
-#else
-      double gf[kFarCap][P];
-#pragma unroll
-      for (int s = 0; s < kFarCap; ++s) far_row((dbg & 1) ? (unsigned)(slice * 64 + lane) : h.f[s], gf[s]);
-      unsigned wd[HW];
-#pragma unroll
-      for (int j = 0; j < HW; ++j) wd[j] = entry_word(h, j, k, b1);
-      MI_STAMP(2 + 8 * (t - t0) + 1, (double)wd[0]);  // this slice's matrix words were there
-      if (!(dbg & 8)) load_head(h, q0, more ? nslice : slice);
-#endif
-      if (!(dbg & 2)) epi.request(slice);  // the epilogue rows of THIS slice: the entries' work lies between here and their use
+      epi.request(slice);  // the epilogue rows of THIS slice: the entries' work lies between here and their use
       // the gathers (and only they: 2 P + HW + 2 + 2 P pinned loads were issued behind them) -> far slots
       if constexpr (FARC) {
 #pragma unroll
@@ -769,19 +714,13 @@ __device__ __forceinline__ void sell_window(const SellView &A, const WinView &W,
         const LdsDouble *l = L + (unsigned)(slot_own * 64 + lane) * (unsigned)RS;
 #pragma unroll
         for (int c = 0; c < P; ++c) vrow[c] = l[c];
-        if constexpr (EpiScratch<Epi>::value) {
-          if (!(dbg & 4)) epi.end(slice, acc, vrow, L + far_rows0);
-        } else {
-          if (!(dbg & 4)) epi.end(slice, acc, vrow);
-        }
+        epi.end(slice, acc, vrow);
         MI_STAMP(2 + 8 * (t - t0) + 5, acc[0]);  // epilogue done, stores issued
       }
-#ifndef MI_WIN_NO_FARAHEAD
 #pragma unroll
       for (int s = 0; s < kFarCap; ++s)
 #pragma unroll
         for (int c = 0; c < P; ++c) gf[s][c] = gn[s][c];
-#endif
       have = more;
       slice = nslice;
       k = q0;

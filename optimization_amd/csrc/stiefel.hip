@@ -1,5 +1,6 @@
-// stiefel.hip -- Stiefel manifold St(n,p) (embedded metric) kernels for p <= 8 -- rows of 9 ... 16 doubles are routed to
-// the tall-row family of stiefel_tall.hip by the entry points below -- and the Rayleigh-quotient
+// stiefel.hip -- Stiefel manifold St(n,p) (embedded metric) kernels for p <= 8 -- the one-pass Hessian of rows of 5 ... 8
+// doubles lives in stiefel_wide.h, rows of 9 ... 16 doubles are routed to the tall-row family of stiefel_tall.hip by the
+// entry points below -- and the Rayleigh-quotient
 // problem  f(X) = .5 tr(X' A X):  the Objective / QuadraticModel / RiemannianMetric / Retraction
 // callables a TNT client supplies (Riemannian/Concepts.h:44-112).  The reference ships only the
 // S^2 = St(3,1) lambdas of tests/TNT_unit_test.cpp:73-117; these are their n x p generalisation:
@@ -31,28 +32,14 @@ namespace {
 
 enum { POST_SYM = 1, POST_INVSQRT = 2 };
 
-// (a scheduling fence behind every column of the three P x P products: without it the scheduler issues all 192 LDS
-// reads of a row up front -- 128 more live doubles -- and the kernel loses its second wave per SIMD)
-#ifndef MI_WIDE_NO_SCHED
-#define MI_WIDE_SCHED() __builtin_amdgcn_sched_barrier(0)
-#else
-#define MI_WIDE_SCHED()
-#endif
-#ifndef MI_WIDE_CHUNK
-#define MI_WIDE_CHUNK 2
-#endif
-#ifndef MI_WIDE_CHUNK_FROM
-#define MI_WIDE_CHUNK_FROM 7   // rows of >= this many doubles gather in chunks of MI_WIDE_CHUNK entries
-#endif
-#ifndef MI_WIDE_QUAD_CHUNK
-#define MI_WIDE_QUAD_CHUNK 8   // entries per chunk step of the quad-layout pass (16 bytes per entry and lane)
-#endif
-#ifndef MI_WIDE_QUAD_WAVES
-#define MI_WIDE_QUAD_WAVES 2   // waves per SIMD of the quad-layout pass (<= 168 registers: 3 would fit)
-#endif
-#ifndef MI_WIDE_WAVES
-#define MI_WIDE_WAVES 2        // waves per SIMD the kernel is held to (measured: 3 -- 168 registers, p <= 7 -- is 3-6 % slower)
-#endif
+// A scheduling fence behind every column of the P x P products of a wide row (p > 4): without it the scheduler issues
+// all 192 LDS reads of a row up front -- 128 more live doubles -- and the kernel loses its second wave per SIMD.
+__device__ __forceinline__ void wide_sched() { __builtin_amdgcn_sched_barrier(0); }
+// entries per chunk of sell_stream (spmm_core.h CHK) by row width: rows of 7 and 8 doubles gather two at a time
+template <int P>
+struct StChunk {
+  static constexpr int value = P >= 7 ? 2 : kSpmmChunk;
+};
 
 
 // ---- small dense helpers (device) --------------------------------------------------------
@@ -277,7 +264,7 @@ __global__ __launch_bounds__(StBlk<P>::threads) void k_st_spmm_gram_stream(SellV
         for (int b = 0; b < P; ++b) G[a * P + b] += x[a] * acc[b];
     }
   } epi{A, X, V, Z, SmR, SmL, G, lane, {}, {}};
-  sell_stream<P, HALO, PK, Epi, NW, (P >= MI_WIDE_CHUNK_FROM ? MI_WIDE_CHUNK : MI_SPMM_CHUNK)>(
+  sell_stream<P, HALO, PK, Epi, NW, StChunk<P>::value>(
       A, s0 + (size_t)__builtin_amdgcn_readfirstlane(w), s1, lane, V, vt, epi);
   store_sym_partials<P>(G, lds, partials);
 }
@@ -463,8 +450,8 @@ __global__ __launch_bounds__(HW > 0 ? kWinBlock : kBlock) void k_st_hess_fused(S
     if constexpr (HALO)
       sell_window<P, HW, true, (FAR >= 1), false>(A, Wv, t0, t1, wu, lane, V, vt, ring, epi, hwait.halo_lo, hwait.halo_hi);
     else
-      // (far rows as coalesced images, sell_window FARC: 26.7-26.9 us either way at p = 3 -- the gathers stay)
-      sell_window<P, HW, false, (FAR >= 1), (FAR == 2), Epi, P, (FAR >= 1) && (MI_WIN_FARC >= 2)>(A, Wv, t0, t1, wu, lane, V, vt, ring, epi);
+      // (FARC = false: far rows as coalesced images change nothing at p <= 3, the gathers stay -- EXPERIMENTS.md "Decided knobs")
+      sell_window<P, HW, false, (FAR >= 1), (FAR == 2), Epi, P, false>(A, Wv, t0, t1, wu, lane, V, vt, ring, epi);
   } else {
     sell_stream<P, HALO, PK>(A, s0 + (size_t)wu, s1, lane, V, vt, epi);
   }
@@ -483,537 +470,7 @@ __global__ __launch_bounds__(HW > 0 ? kWinBlock : kBlock) void k_st_hess_fused(S
 #endif
 }
 
-// ---- rows wider than 4 doubles (p = 5 ... 8) ------------------------------------------------------------------------------
-// The one-pass Hessian in its recurrence form for wide rows.  Same schedule and the same per-row arithmetic as
-// k_st_hess_fused<P, ., ., RECUR = true, ...> -- Z = A V - V S, out = Z - X M with M = G(p) from STPCG's recurrence, the
-// three curvature dots and the packed Gram sym(Y'out - (X'out) S) of the output in the epilogue of the only pass -- but
-// laid out for what p = 8 costs: a row is 64 bytes, three P x P products per row, 3 + P (P + 1) / 2 <= 39 accumulators
-// per lane.  So: 256-thread workgroups (one wave per SIMD, the whole vector register file to itself instead of the 128
-// registers a 1024-thread workgroup leaves a wave), S and M in LDS (every lane reads the same address: broadcast reads,
-// no bank conflicts) instead of 2 x 64 replicated registers, up to kMaxRows partial rows.
-constexpr int kWideBlock = 256, kWideWaves = kWideBlock / 64;
-// first slice of workgroup lb's range: the planned runs of whole 4-slice tiles (sparse.hip window_bounds: cut so that
-// the far stride of the matrix -- the plane stride of a 3-D stencil -- is a whole number of runs, a far row then is
-// some other workgroup's own row at the same moment of the kernel) or equal shares
-__device__ __forceinline__ size_t wide_first_slice(size_t nslices, unsigned lb, unsigned nb, const int *bounds) {
-  if (bounds) {
-    const size_t s = (size_t)bounds[lb] * kWideWaves;
-    return s < nslices ? s : nslices;
-  }
-  return (nslices * lb) / nb;
-}
-template <int P>
-struct WideWaves {
-  static constexpr int value = P <= 7 ? MI_WIDE_WAVES : 2;
-};
-template <int P, bool HALO, bool PK>
-__global__ __launch_bounds__(kWideBlock) __attribute__((amdgpu_waves_per_eu(WideWaves<P>::value, WideWaves<P>::value))) void k_st_hess_wide(SellView A, const CgState *__restrict__ st,
-                                                             const double *__restrict__ V, const double *__restrict__ X,
-                                                             const double *__restrict__ Y, const double *__restrict__ S,
-                                                             const double *__restrict__ gdir, double *__restrict__ out,
-                                                             double *__restrict__ partials, HaloWaitArg<HALO> hwait,
-                                                             const int *__restrict__ bounds) {
-  constexpr int NS = SymIdx<P>::NS, KC = 3 + NS;
-  __shared__ double lds[KC * kWideWaves];
-  __shared__ double vt[PK ? 256 : 1];
-  __shared__ double Sm[P * P], Mm[P * P];
-#ifndef MI_WIDE_ABLATE_MATH  // (the timing experiments produce wrong iterates: their launches must not turn into no-ops)
-  if (st && st->mode != CG_RUN) return;
-#endif
-  if constexpr (HALO) halo_wait(hwait.w);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (PK) vt[threadIdx.x] = A.vtab[threadIdx.x];
-  if (threadIdx.x < P * P) {
-    const int aa = threadIdx.x / P, b = threadIdx.x % P;
-    Sm[threadIdx.x] = S[threadIdx.x];
-    Mm[threadIdx.x] = gdir[SLOT_GDIR_P + (aa <= b ? SymIdx<P>::at(aa, b) : SymIdx<P>::at(b, aa))];
-  }
-  __syncthreads();
-  const unsigned nb = gridDim.x, lb = xcd_remap(blockIdx.x, nb);
-  const size_t s0 = wide_first_slice(A.nslices, lb, nb, bounds), s1 = wide_first_slice(A.nslices, lb + 1, nb, bounds);
-  double a[KC];
-#pragma unroll
-  for (int i = 0; i < KC; ++i) a[i] = 0;
-  struct Epi {
-    const SellView &A;
-    const double *__restrict__ X, *__restrict__ Y, *__restrict__ V;
-    double *__restrict__ out;
-    const double *Sm, *Mm;
-    double (&a)[KC];
-    int lane;
-    double x[P], y[P], v[P];
-    __device__ __forceinline__ unsigned lane_off(size_t slice) const {
-      return ((unsigned)slice * 64u + (unsigned)lane < (unsigned)A.n) ? (unsigned)lane * (unsigned)(P * 8) : 0u;
-    }
-    __device__ __forceinline__ const double *row_of(const double *F, size_t slice, unsigned off) const {
-      return reinterpret_cast<const double *>(reinterpret_cast<const char *>(F) + (unsigned)slice * (unsigned)(64 * P * 8) + off);
-    }
-    __device__ __forceinline__ void begin(size_t slice) {
-      const unsigned off = lane_off(slice);
-      const double *xs = row_of(X, slice, off), *vs = row_of(V, slice, off), *ys = row_of(Y, slice, off);
-#pragma unroll
-#ifdef MI_WIDE_ABLATE_OWN  // (timing experiment only: X and Y rows not read -- wrong results)
-      for (int c = 0; c < P; ++c) { v[c] = vs[c]; x[c] = v[c] + 1.0; y[c] = v[c] - 1.0; }
-#else
-      for (int c = 0; c < P; ++c) { x[c] = xs[c]; v[c] = vs[c]; y[c] = ys[c]; }
-#endif
-    }
-    __device__ __forceinline__ void end(size_t slice, double (&acc)[P]) {
-      if ((unsigned)slice * 64u + (unsigned)lane >= (unsigned)A.n) return;
-      // (S and M are re-read from LDS for every row: loop-invariant code motion must not park 128 doubles in registers)
-      asm volatile("" ::: "memory");
-      double *os = reinterpret_cast<double *>(reinterpret_cast<char *>(out) + (unsigned)slice * (unsigned)(64 * P * 8) +
-                                              lane_off(slice));
-#ifndef MI_WIDE_ABLATE_MATH  // (timing experiment only: wrong results)
-#pragma unroll
-      for (int b = 0; b < P; ++b) {
-        double t = 0;
-#pragma unroll
-        for (int aa = 0; aa < P; ++aa) t += v[aa] * Sm[aa * P + b];
-        acc[b] -= t;  // Z = A V - V S
-        MI_WIDE_SCHED();
-      }
-#endif
-      double o[P];
-#pragma unroll
-      for (int b = 0; b < P; ++b) {
-        double t = 0;
-#ifndef MI_WIDE_ABLATE_MATH
-#pragma unroll
-        for (int aa = 0; aa < P; ++aa) t += x[aa] * Mm[aa * P + b];
-#endif
-        o[b] = acc[b] - t;  // Z - X M
-#ifdef MI_WIDE_ABLATE_STORE  // (timing experiment only: one double of the row stored)
-        if (b == 0) os[b] = acc[0] + acc[P - 1];
-#else
-        os[b] = o[b];
-#endif
-        a[0] += v[b] * o[b]; a[1] += o[b] * o[b]; a[2] += v[b] * v[b];
-        MI_WIDE_SCHED();
-      }
-      double os_[P];  // packed sym(y o' - x (o S)'): the Gram of this output row
-#pragma unroll
-      for (int b = 0; b < P; ++b) {
-        double t = 0;
-#ifndef MI_WIDE_ABLATE_MATH
-#pragma unroll
-        for (int aa = 0; aa < P; ++aa) t += o[aa] * Sm[aa * P + b];
-#endif
-        os_[b] = t;
-        MI_WIDE_SCHED();
-      }
-#ifndef MI_WIDE_ABLATE_GRAM
-#pragma unroll
-      for (int aa = 0; aa < P; ++aa)
-#pragma unroll
-        for (int b = aa; b < P; ++b) {
-          const double gab = y[aa] * o[b] - x[aa] * os_[b];
-          const double gba = y[b] * o[aa] - x[b] * os_[aa];
-          a[3 + SymIdx<P>::at(aa, b)] += (aa == b) ? gab : .5 * (gab + gba);
-        }
-#else
-      a[3] += y[0] * os_[0] + x[P - 1];
-#endif
-    }
-  } epi{A, X, Y, V, out, Sm, Mm, a, lane, {}, {}, {}};
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  sell_stream<P, HALO, PK, Epi, kWideWaves, (P >= MI_WIDE_CHUNK_FROM ? MI_WIDE_CHUNK : MI_SPMM_CHUNK)>(A, s0 + (size_t)wu, s1, lane, V, vt, epi);
-  block_partials_store_nw<KC, kWideWaves>(a, lds, partials);
-}
-
-// The wide-row pass in WINDOW form (r06): the same epilogue as k_st_hess_wide (S and M in LDS, 3 + P (P +
-// 1) / 2 partial components), but the product A V through spmm_core.h's sell_window instead of sell_stream -- the near
-// rows of V come out of an LDS ring that is filled by coalesced 512-byte loads of whole 64-row chunks (a chunk of a
-// row-major field is 64 P contiguous doubles), only the two far rows of a row are gathered lane by lane, and the far
-// columns are computed (pure far structure).  What the lane-per-row form pays for -- seven neighbour gathers of P
-// strided 8-byte loads each, every wave instruction touching 64 half-lines (profiles/r05_wide_ablation.txt) -- is gone;
-// the own X and Y rows remain lane-per-row loads.  One context, packed matrix with a window (sparse.hip build_window),
-// no halo.  The ring is dynamic LDS sized for the matrix's own window: (nc 64 + 1 + far slots) P doubles.
-#ifndef MI_WIDEWIN_COAL
-#define MI_WIDEWIN_COAL 0   // 1: own X / Y rows as coalesced memory images, transposed through the wave's far slots (measured slower)
-#endif
-#ifndef MI_WIDEWIN_X16
-#define MI_WIDEWIN_X16 1    // P = 6: own X / Y rows by 16-byte asm loads (k_st_hess_widewin Epi::request)
-#endif
-#ifndef MI_WIDEWIN_3WAVES_UPTO
-#define MI_WIDEWIN_3WAVES_UPTO 3   // (experiment: 4 = three workgroups per CU at p = 4)
-#endif
-#ifndef MI_WIDEWIN_2WAVES_UPTO
-#define MI_WIDEWIN_2WAVES_UPTO 7   // widths held to 256 VGPRs (two workgroups per CU); wider: one workgroup per CU
-#endif
-// ring rows of the wide window form (spmm_core.h sell_window RS): at P = 8 rows 64 bytes apart put the row-by-row reads
-// of a wave on a sixteenth of the LDS banks (218 us; 9 doubles apart: 102 us -- still behind the quad layout's 80, so
-// p = 8 does not take this form by default); at P = 6 the padding changes nothing (57.7 us either way) and costs
-// 11-14 registers: not applied
-template <int P>
-struct WideRing {
-  static constexpr int stride = (P == 8) ? 9 : P;
-};
-template <int P, int HW, bool FARD>
-__global__ __launch_bounds__(kWinBlock) __attribute__((amdgpu_waves_per_eu(P <= MI_WIDEWIN_3WAVES_UPTO ? 3 : P <= MI_WIDEWIN_2WAVES_UPTO ? 2 : 1, P <= MI_WIDEWIN_3WAVES_UPTO ? 3 : P <= MI_WIDEWIN_2WAVES_UPTO ? 2 : 1))) void k_st_hess_widewin(
-    SellView A, WinView Wv, const CgState *__restrict__ st, const double *__restrict__ V, const double *__restrict__ X,
-    const double *__restrict__ Y, const double *__restrict__ S, const double *__restrict__ gdir, double *__restrict__ out,
-    double *__restrict__ partials) {
-  static_assert(kWideWaves == kWinWaves, "one workgroup shape");
-  constexpr int KC = DirComps<P>::value;  // 3 + P (P + 1) / 2 (P = 4: padded to 16, the pads stay zero)
-  __shared__ double lds[KC * kWideWaves];
-  __shared__ double vt[256];
-  __shared__ double Sm[P * P], Mm[P * P];
-  extern __shared__ __attribute__((aligned(16))) double ring_dyn[];
-#if !defined(MI_WIDE_ABLATE_MATH) && !defined(MI_WIDE_ABLATE_OWN) && !defined(MI_WIDE_ABLATE_STORE)
-  if (st && st->mode != CG_RUN) return;   // (the timing experiments produce wrong iterates: their launches must not turn into no-ops)
-#endif
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  vt[threadIdx.x] = A.vtab[threadIdx.x];
-  if (threadIdx.x < P * P) {
-    const int aa = threadIdx.x / P, b = threadIdx.x % P;
-    Sm[threadIdx.x] = S[threadIdx.x];
-    Mm[threadIdx.x] = gdir[SLOT_GDIR_P + (aa <= b ? SymIdx<P>::at(aa, b) : SymIdx<P>::at(b, aa))];
-  }
-  // (sell_window's barrier behind the ring fill publishes vt, Sm and Mm too)
-  const unsigned nb = gridDim.x, lb = xcd_remap(blockIdx.x, nb);
-  double a[KC];
-#pragma unroll
-  for (int i = 0; i < KC; ++i) a[i] = 0;
-  struct Epi {
-    const SellView &A;
-    const double *__restrict__ X, *__restrict__ Y;
-    double *__restrict__ out;
-    const double *Sm, *Mm;
-    double (&a)[KC];
-    int lane;
-    double xn[P], yn[P];
-    __device__ __forceinline__ unsigned lane_off(size_t slice) const {
-      return ((unsigned)slice * 64u + (unsigned)lane < (unsigned)A.n) ? (unsigned)lane * (unsigned)(P * 8) : 0u;
-    }
-    __device__ __forceinline__ const double *row_of(const double *F, size_t slice, unsigned off) const {
-      return reinterpret_cast<const double *>(reinterpret_cast<const char *>(F) + (unsigned)slice * (unsigned)(64 * P * 8) + off);
-    }
-#if MI_WIDEWIN_COAL && !defined(MI_WIDE_ABLATE_OWN)
-    // The slice's rows of X and Y are 64 P consecutive doubles each: P coalesced 512-byte loads per field (lane l: the
-    // doubles l, 64 + l, ...) instead of P strided 8-byte loads per lane -- at 6 doubles a row a wave instruction of
-    // those touches 24 lines, and the texture path, not the bytes, then paces the pass (profiles/r06_widewin_ablation.txt:
-    // -7 us without them).  The images become rows again through the wave's far slots, free once the entries are done.
-    // MEASURED (r06, same box, alternating): p = 5 / 6 / 7: 46.3 / 56.1 / 74.8 us without -> 47.5 / 57.0 / 82.3 us with:
-    // the 4 P extra LDS operations per row cost more than the lines save.  Not the default.
-    using wants_scratch = void;
-    __device__ __forceinline__ void request(size_t slice) {
-      const unsigned nPbytes = (unsigned)(A.n * P * 8);
-      const unsigned b0 = (unsigned)slice * (unsigned)(64 * P * 8) + (unsigned)lane * 8u;
-#pragma unroll
-      for (int c = 0; c < P; ++c) {
-        const unsigned b = b0 + (unsigned)c * 512u;
-        xn[c] = pinned_load(reinterpret_cast<const double *>(reinterpret_cast<const char *>(X) + (b < nPbytes ? b : 0u)));
-      }
-#pragma unroll
-      for (int c = 0; c < P; ++c) {
-        const unsigned b = b0 + (unsigned)c * 512u;
-        yn[c] = pinned_load(reinterpret_cast<const double *>(reinterpret_cast<const char *>(Y) + (b < nPbytes ? b : 0u)));
-      }
-    }
-    __device__ __forceinline__ void end(size_t slice, double (&acc)[P], const double (&v)[P], LdsDouble *scratch) {
-      constexpr int RS = WideRing<P>::stride;
-      image_store<P, RS>(scratch, lane, xn);
-      image_store<P, RS>(scratch + 64 * RS, lane, yn);
-      image_row<P, RS>(scratch, lane, xn);   // (one wave: its LDS operations complete in order)
-      image_row<P, RS>(scratch + 64 * RS, lane, yn);
-      end(slice, acc, v);
-    }
-#elif MI_WIDEWIN_X16 && !defined(MI_WIDE_ABLATE_OWN)
-    // P = 4, 6: a row is two / three 16-byte pieces -- P / 2 global_load_dwordx4 per field instead of P 8-byte loads (half
-    // the texture-path instructions, half the hits on lines still pending: p = 6 57.5 -> 55.8 us, same box, alternating;
-    // at P = 8 in this form 100 -> 105 us, not used).  There is no ordered (pinned) 16-byte load to be had from the
-    // compiler, so these are asm statements: absent from hipcc's s_waitcnt bookkeeping, waited for by the explicit
-    // vmcnt(0) in arrive() (they are the newest loads of the tile: a wait hipcc computes for an older load only gets longer).
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    v2d xq[3], yq[3];
-    __device__ __forceinline__ void request(size_t slice) {
-      if constexpr (P == 4 || P == 6) {
-        const unsigned off = (unsigned)slice * (unsigned)(64 * P * 8) + lane_off(slice);
-#pragma unroll
-        for (int c = 0; c < P / 2; ++c)
-          asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(xq[c]) : "v"(off), "s"(X), "n"(16 * c) : "memory");
-#pragma unroll
-        for (int c = 0; c < P / 2; ++c)
-          asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(yq[c]) : "v"(off), "s"(Y), "n"(16 * c) : "memory");
-      } else {
-        const unsigned off = lane_off(slice);
-        const double *xs = row_of(X, slice, off), *ys = row_of(Y, slice, off);
-#pragma unroll
-        for (int c = 0; c < P; ++c) xn[c] = pinned_load(xs + c);
-#pragma unroll
-        for (int c = 0; c < P; ++c) yn[c] = pinned_load(ys + c);
-      }
-    }
-    __device__ __forceinline__ void arrive() {
-      if constexpr (P == 6)
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(xq[0]), "+v"(xq[1]), "+v"(xq[2]), "+v"(yq[0]), "+v"(yq[1]), "+v"(yq[2])::"memory");
-      else if constexpr (P == 4)
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(xq[0]), "+v"(xq[1]), "+v"(yq[0]), "+v"(yq[1])::"memory");
-      if constexpr (P == 4 || P == 6) {
-#pragma unroll
-        for (int c = 0; c < P / 2; ++c) { xn[2 * c] = xq[c].x; xn[2 * c + 1] = xq[c].y; yn[2 * c] = yq[c].x; yn[2 * c + 1] = yq[c].y; }
-      }
-    }
-#else
-    __device__ __forceinline__ void request(size_t slice) {
-      const unsigned off = lane_off(slice);
-      const double *xs = row_of(X, slice, off), *ys = row_of(Y, slice, off);
-#pragma unroll
-#ifdef MI_WIDE_ABLATE_OWN   // (timing experiment only: X and Y rows not read -- wrong results)
-      for (int c = 0; c < P; ++c) { xn[c] = (double)(off + c); yn[c] = xn[c] - 1.0; }
-      (void)xs; (void)ys;
-#else
-      for (int c = 0; c < P; ++c) xn[c] = pinned_load(xs + c);
-#pragma unroll
-      for (int c = 0; c < P; ++c) yn[c] = pinned_load(ys + c);
-#endif
-    }
-#endif
-    __device__ __forceinline__ void end(size_t slice, double (&acc)[P], const double (&v)[P]) {
-#if MI_WIDEWIN_X16 && !MI_WIDEWIN_COAL && !defined(MI_WIDE_ABLATE_OWN)
-      arrive();  // (every lane: the wait is not a matter of the lane's row)
-#endif
-      if ((unsigned)slice * 64u + (unsigned)lane >= (unsigned)A.n) return;
-      // (S and M are re-read from LDS for every row: loop-invariant code motion must not park 128 doubles in registers)
-      asm volatile("" ::: "memory");
-      double *os = reinterpret_cast<double *>(reinterpret_cast<char *>(out) + (unsigned)slice * (unsigned)(64 * P * 8) +
-                                              lane_off(slice));
-#pragma unroll
-      for (int b = 0; b < P; ++b) {
-        double t = 0;
-#ifndef MI_WIDE_ABLATE_MATH
-#pragma unroll
-        for (int aa = 0; aa < P; ++aa) t += v[aa] * Sm[aa * P + b];
-#endif
-        acc[b] -= t;  // Z = A V - V S
-        MI_WIDE_SCHED();
-      }
-      double o[P];
-#pragma unroll
-      for (int b = 0; b < P; ++b) {
-        double t = 0;
-#ifndef MI_WIDE_ABLATE_MATH
-#pragma unroll
-        for (int aa = 0; aa < P; ++aa) t += xn[aa] * Mm[aa * P + b];
-#endif
-        o[b] = acc[b] - t;  // Z - X M
-#ifdef MI_WIDE_ABLATE_STORE  // (timing experiment only: one double of the row stored)
-        if (b == 0) os[b] = acc[0] + acc[P - 1];
-#else
-        os[b] = o[b];  // (non-temporal stores / loads of the own rows: 58 -> 63-74 us at p = 6, EXPERIMENTS.md r06)
-#endif
-        a[0] += v[b] * o[b]; a[1] += o[b] * o[b]; a[2] += v[b] * v[b];
-        MI_WIDE_SCHED();
-      }
-      double os_[P];  // packed sym(y o' - x (o S)'): the Gram of this output row
-#pragma unroll
-      for (int b = 0; b < P; ++b) {
-        double t = 0;
-#ifndef MI_WIDE_ABLATE_MATH
-#pragma unroll
-        for (int aa = 0; aa < P; ++aa) t += o[aa] * Sm[aa * P + b];
-#endif
-        os_[b] = t;
-        MI_WIDE_SCHED();
-      }
-#pragma unroll
-      for (int aa = 0; aa < P; ++aa)
-#pragma unroll
-        for (int b = aa; b < P; ++b) {
-          const double gab = yn[aa] * o[b] - xn[aa] * os_[b];
-          const double gba = yn[b] * o[aa] - xn[b] * os_[aa];
-          a[3 + SymIdx<P>::at(aa, b)] += (aa == b) ? gab : .5 * (gab + gba);
-        }
-    }
-  } epi{A, X, Y, out, Sm, Mm, a, lane, {}, {}};
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  const int ntiles = (int)((A.nslices + kWinWaves - 1) / kWinWaves), per = (ntiles + (int)nb - 1) / (int)nb;
-  int t0 = (int)lb * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
-  if (Wv.bounds) {
-    t0 = scalar_int(Wv.bounds, lb);
-    t1 = scalar_int(Wv.bounds, lb + 1);
-  }
-  if (t0 >= t1) __syncthreads();  // (sell_window returns at once: the tables above still need their barrier)
-  sell_window<P, HW, false, FARD, false, Epi, WideRing<P>::stride, FARD && MI_WIN_FARC>(A, Wv, t0, t1, wu, lane, V, vt, ring_dyn, epi);
-  __syncthreads();
-  block_partials_store_nw<KC, kWideWaves>(a, lds, partials);
-}
-
-// The same pass in the QUAD layout of spmm_core.h (sell_stream_quad): lane (g, q) holds columns 2q, 2q + 1 of the rows
-// 16 t + g of its wave's slice, every load and store of a row is 64 contiguous bytes per quad.  A row's full width --
-// the left operands of the three products and of the Gram -- comes from the quad's four lanes by DPP broadcasts; S and M
-// sit in LDS padded to 8 x 8 with zero columns (a lane reads its two columns of a row of the matrix as one 16-byte
-// read); the Gram of the output is accumulated RAW (y_a o_b - x_a (o S)_b for the lane's two b: 2 P accumulators instead
-// of P (P + 1) / 2) and symmetrised once, at the end, through LDS.
-template <int CTRL>
-__device__ __forceinline__ double dpp_quad_f64(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-// full[2 i + c] = the value of column 2 i + c held by lane i of the quad
-template <int P>
-__device__ __forceinline__ void quad_row(const double (&own)[2], double (&full)[8]) {
-  full[0] = dpp_quad_f64<0x00>(own[0]); full[1] = dpp_quad_f64<0x00>(own[1]);
-  full[2] = dpp_quad_f64<0x55>(own[0]); full[3] = dpp_quad_f64<0x55>(own[1]);
-  full[4] = dpp_quad_f64<0xAA>(own[0]);
-  if constexpr (P > 5) full[5] = dpp_quad_f64<0xAA>(own[1]);
-  if constexpr (P > 6) full[6] = dpp_quad_f64<0xFF>(own[0]);
-  if constexpr (P > 7) full[7] = dpp_quad_f64<0xFF>(own[1]);
-}
-template <int P, bool HALO, bool PK>
-__global__ __launch_bounds__(kWideBlock) __attribute__((amdgpu_waves_per_eu(MI_WIDE_QUAD_WAVES, MI_WIDE_QUAD_WAVES))) void k_st_hess_wideq(SellView A, const CgState *__restrict__ st,
-                                                             const double *__restrict__ V, const double *__restrict__ X,
-                                                             const double *__restrict__ Y, const double *__restrict__ S,
-                                                             const double *__restrict__ gdir, double *__restrict__ out,
-                                                             double *__restrict__ partials, HaloWaitArg<HALO> hwait,
-                                                             const int *__restrict__ bounds) {
-  constexpr int NS = SymIdx<P>::NS, KC = 3 + NS;
-  __shared__ double lds[3 * kWideWaves];
-  __shared__ double graw[kWideWaves][P][8];
-  __shared__ double vt[PK ? 256 : 1];
-  __shared__ __attribute__((aligned(16))) double Sm[P * 8], Mm[P * 8];
-#ifndef MI_WIDEQ_ABLATE_EPI
-  if (st && st->mode != CG_RUN) return;
-#endif
-  if constexpr (HALO) halo_wait(hwait.w);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (PK) vt[threadIdx.x] = A.vtab[threadIdx.x];
-  if (threadIdx.x < P * 8) {
-    const int aa = threadIdx.x >> 3, b = threadIdx.x & 7;
-    Sm[threadIdx.x] = b < P ? S[aa * P + b] : 0.0;
-    Mm[threadIdx.x] = b < P ? gdir[SLOT_GDIR_P + (aa <= b ? SymIdx<P>::at(aa, b) : SymIdx<P>::at(b, aa))] : 0.0;
-  }
-  __syncthreads();
-  const unsigned nb = gridDim.x, lb = xcd_remap(blockIdx.x, nb);
-  const size_t s0 = wide_first_slice(A.nslices, lb, nb, bounds), s1 = wide_first_slice(A.nslices, lb + 1, nb, bounds);
-  double a[3] = {0, 0, 0};
-  double G[P][2];
-#pragma unroll
-  for (int i = 0; i < P; ++i) G[i][0] = G[i][1] = 0;
-  struct Epi {
-    const SellView &A;
-    const double *__restrict__ X, *__restrict__ Y, *__restrict__ V;
-    double *__restrict__ out;
-    const double *Sm, *Mm;
-    double (&a)[3];
-    double (&G)[P][2];
-    int q, g;
-    unsigned o0, o1;
-    __device__ __forceinline__ unsigned row_off(size_t slice, int t) const {  // (rows past the end re-read the slice's first)
-      const unsigned r = (unsigned)slice * 64u + (unsigned)(16 * t + g);
-      return (r < (unsigned)A.n ? r : (unsigned)slice * 64u) * (unsigned)(P * 8);
-    }
-    __device__ __forceinline__ void begin(size_t slice, int t, double (&x)[2], double (&v)[2], double (&y)[2]) const {
-      const unsigned off = row_off(slice, t);
-      QuadCols<P>::load(reinterpret_cast<const char *>(X), off, o0, o1, x[0], x[1]);
-      QuadCols<P>::load(reinterpret_cast<const char *>(V), off, o0, o1, v[0], v[1]);
-      QuadCols<P>::load(reinterpret_cast<const char *>(Y), off, o0, o1, y[0], y[1]);
-    }
-    __device__ __forceinline__ void end(size_t slice, int t, double (&acc)[2], const double (&x)[2], const double (&v)[2],
-                                        const double (&y)[2]) {
-      const bool c0 = 2 * q < P, c1 = 2 * q + 1 < P;
-      const double2 *S2 = reinterpret_cast<const double2 *>(Sm) + q, *M2 = reinterpret_cast<const double2 *>(Mm) + q;
-      // (S and M are re-read from LDS for every row: loop-invariant code motion must not park them in registers)
-      asm volatile("" ::: "memory");
-      const bool live = (unsigned)slice * 64u + (unsigned)(16 * t + g) < (unsigned)A.n;
-      const bool u0 = live && c0, u1 = live && c1;
-      const double vv[2] = {u0 ? v[0] : 0.0, u1 ? v[1] : 0.0};
-      const double xx[2] = {u0 ? x[0] : 0.0, u1 ? x[1] : 0.0};
-      const double yy[2] = {u0 ? y[0] : 0.0, u1 ? y[1] : 0.0};
-      double z[2] = {u0 ? acc[0] : 0.0, u1 ? acc[1] : 0.0};
-#ifdef MI_WIDEQ_ABLATE_EPI  // (timing experiment only: the row epilogue reduced to the store -- wrong results)
-      {
-        char *ob = reinterpret_cast<char *>(out);
-        const unsigned ro = row_off(slice, t);
-        if (u0) *reinterpret_cast<double2 *>(ob + (ro + o0)) = make_double2(z[0] + xx[0] + yy[0] + vv[0], z[1] + xx[1] + yy[1] + vv[1]);
-        a[0] += z[0];
-        return;
-      }
-#endif
-      double vf[8], xf[8], yf[8], of[8];
-      quad_row<P>(vv, vf);
-      quad_row<P>(xx, xf);
-#pragma unroll
-      for (int aa = 0; aa < P; ++aa) {  // Z = A V - V S, then out = Z - X M (the lane's two columns)
-        const double2 sc = S2[aa * 4];
-        z[0] -= vf[aa] * sc.x; z[1] -= vf[aa] * sc.y;
-      }
-      MI_WIDE_SCHED();
-#pragma unroll
-      for (int aa = 0; aa < P; ++aa) {
-        const double2 mc = M2[aa * 4];
-        z[0] -= xf[aa] * mc.x; z[1] -= xf[aa] * mc.y;
-      }
-      MI_WIDE_SCHED();
-      {
-        char *ob = reinterpret_cast<char *>(out);
-        const unsigned ro = row_off(slice, t);
-        if constexpr (P % 2 == 0) {
-          if (u0) *reinterpret_cast<double2 *>(ob + (ro + o0)) = make_double2(z[0], z[1]);
-        } else {
-          if (u0) *reinterpret_cast<double *>(ob + (ro + o0)) = z[0];
-          if (u1) *reinterpret_cast<double *>(ob + (ro + o1)) = z[1];
-        }
-      }
-      a[0] += vv[0] * z[0]; a[0] += vv[1] * z[1];
-      a[1] += z[0] * z[0]; a[1] += z[1] * z[1];
-      a[2] += vv[0] * vv[0]; a[2] += vv[1] * vv[1];
-      quad_row<P>(z, of);
-      double os_[2] = {0, 0};  // (o S), the lane's two columns
-#pragma unroll
-      for (int aa = 0; aa < P; ++aa) {
-        const double2 sc = S2[aa * 4];
-        os_[0] += of[aa] * sc.x; os_[1] += of[aa] * sc.y;
-      }
-      MI_WIDE_SCHED();
-      quad_row<P>(yy, yf);
-#pragma unroll
-      for (int aa = 0; aa < P; ++aa) {  // raw Gram of this output row: y_a o_b - x_a (o S)_b
-        G[aa][0] += yf[aa] * z[0] - xf[aa] * os_[0];
-        G[aa][1] += yf[aa] * z[1] - xf[aa] * os_[1];
-      }
-    }
-  } epi{A, X, Y, V, out, Sm, Mm, a, G, lane & 3, lane >> 2, QuadCols<P>::off0(lane & 3), QuadCols<P>::off1(lane & 3)};
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  sell_stream_quad<P, HALO, PK, Epi, kWideWaves, MI_WIDE_QUAD_CHUNK>(A, s0 + (size_t)wu, s1, lane, V, vt, epi);
-  // the wave's raw Gram: sum over the 16 quads (lane bits 2..5), lanes 0..3 hold columns 2q, 2q + 1
-#pragma unroll
-  for (int aa = 0; aa < P; ++aa)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      double t = G[aa][c];
-#pragma unroll
-      for (int m = 4; m < 64; m <<= 1) t += __shfl_xor(t, m, 64);
-      if (lane < 4) graw[w][aa][2 * lane + c] = t;
-    }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double t = wave_reduce_sum(a[k]);
-    if (lane == 0) lds[k * kWideWaves + w] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < KC) {
-    double t[kWideWaves];
-    if (threadIdx.x < 3) {
-#pragma unroll
-      for (int i = 0; i < kWideWaves; ++i) t[i] = lds[threadIdx.x * kWideWaves + i];
-    } else {
-      int aa = 0, idx = (int)threadIdx.x - 3;  // packed index -> (aa, b), aa <= b
-      while (idx >= P - aa) { idx -= P - aa; ++aa; }
-      const int b = aa + idx;
-#pragma unroll
-      for (int i = 0; i < kWideWaves; ++i) t[i] = aa == b ? graw[i][aa][aa] : .5 * (graw[i][aa][b] + graw[i][b][aa]);
-    }
-#pragma unroll
-    for (int span = 1; span < kWideWaves; span *= 2)
-#pragma unroll
-      for (int i = 0; i + span < kWideWaves; i += 2 * span) t[i] = t[i] + t[i + span];
-    partials[(size_t)threadIdx.x * kMaxRows + blockIdx.x] = t[0];
-  }
-}
+#include "stiefel_wide.h"  // rows wider than 4 doubles (p = 5 ... 8): k_st_hess_wide, k_st_hess_widewin, k_st_hess_wideq
 
 // Gram partial rows of two dense n x P fields.
 //   VARIANT 0: gram(X,Z)              1: Y = X + Z written to out, gram(Y,Y)
@@ -1119,7 +576,7 @@ __global__ __launch_bounds__(StBlk<P>::threads) void k_st_finish(size_t n, const
       const double o = z[b] - t;
       out[row * P + b] = o;
       if (DOTS) { a[0] += vi[b] * o; a[1] += o * o; a[2] += vi[b] * vi[b]; }
-      if (WIDE) MI_WIDE_SCHED();
+      if (WIDE) wide_sched();
     }
     row = rnext;
 #pragma unroll
@@ -1483,14 +940,14 @@ int rq_apply_dir(mi_op *self, const mi_vec *in, mi_vec *out, int gram_count, int
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kWinBlock, pl.lds_bytes) != hipSuccess || occ < 1) occ = 1;
     (void)hipGetLastError();
-    int wgs = std::min(std::min(occ, p <= MI_WIDEWIN_3WAVES_UPTO ? 3 : 2) * ctx->num_cu, kMaxRows);
+    int wgs = std::min(std::min(occ, 2) * ctx->num_cu, kMaxRows);  // (p >= 4: at most two workgroups per CU)
     if (capped) wgs = std::min(wgs, ctx->max_grid);
     MI_TRY(window_bounds(ctx, A, wgs, ntiles, &grid, &bounds));
   } else if (pl.form == ST_HESS_WIDE || pl.form == ST_HESS_WIDEQ) {
-    // 256-thread workgroups, as many per CU as the kernel is held to (WideWaves<P>: one wave per SIMD each): one resident
+    // 256-thread workgroups, as many per CU as the kernel is held to (kWideWavesPerSimd: one wave per SIMD each): one resident
     // round, at most kMaxRows partial rows; several ranks in rows mode need exactly kMaxGrid of them
     const size_t wgs = (A->nslices + kWideWaves - 1) / kWideWaves;
-    const int resident = ctx->num_cu * (pl.form == ST_HESS_WIDEQ ? MI_WIDE_QUAD_WAVES : p <= 7 ? MI_WIDE_WAVES : 2);
+    const int resident = ctx->num_cu * kWideWavesPerSimd;
     grid = ctx->uniform_grid ? kMaxGrid : (int)std::max<size_t>(1, std::min<size_t>(wgs, std::min(resident, kMaxRows)));
     if (!ctx->uniform_grid && capped) grid = std::min(grid, ctx->max_grid);
     if (pl.run_table) MI_TRY(window_bounds(ctx, A, grid, (int)wgs, &grid, &bounds));

@@ -64,7 +64,7 @@ def test_streaming_kernels_that_need_eight_waves_per_simd_stay_within_80_sgprs()
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_asm_loads_of_the_wide_window_pass_are_left_alone_until_their_wait(tmp_path):
-    """k_st_hess_widewin<4 | 6, ...> loads its own X / Y rows by P `global_load_dwordx4` ASM statements (stiefel.hip
+    """k_st_hess_widewin<4 | 6, ...> loads its own X / Y rows by P `global_load_dwordx4` ASM statements (stiefel_wide.h
     Epi::request: there is no ordered 16-byte load to be had from the compiler) and waits for them by an ASM
     `s_waitcnt vmcnt(0)` (Epi::arrive).  hipcc does not know that the registers of an asm load are filled later: a copy or
     a spill of one of them between the load and the wait would move garbage.  This test reads the generated code of every

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Average time of the wide-row one-pass Hessian (k_st_hess_wide) inside 50-iteration solves on St(1e6,p), p = 5 and 8,
-for the library named by MI355OPT_LIB -- the ablation builds (-DMI_WIDE_ABLATE_*, -DMI_ABLATE_GATHER_OWN: wrong
-results, their launches never return early) are compared with the product build in one gpurun call.
+"""Average time of the wide-row one-pass Hessian (k_st_hess_wide*) inside 50-iteration solves on St(1e6,p), p = 5 ... 8
+by default, for the library named by MI355OPT_LIB (the product build when unset).
 Usage: python tools/wide_hess_time.py [p ...]"""
 import sys, json, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
