@@ -771,6 +771,31 @@ MI_API int mi_debug_stiefel_hess_form(int p, int gram_count, const size_t traits
  * (a context that has opted into TWO_KERNEL_STEP counts as WORDS16 = 0), so FAR = 2 says that this context's Hessian
  * pass streams the 16-bit words */
 MI_API int mi_debug_stiefel_hess_form_of(const mi_ctx *ctx, const mi_csr *A, int p, int gram_count, int out[14]);
+/* host-only, read-only: the launch plans of the LOBPCG building blocks (csrc/lobpcg_plan.h) for plain numbers; no GPU.
+ * Flags are 0 / 1.
+ *   kind 0, mi_lobpcg_gram:  in  = {m, ka, kb, S and T are one panel, T = [T1 | T2], every panel 16-byte aligned,
+ *                                   every panel 32-byte aligned, compute units}
+ *                            out = {ok (0: a split T on a shape the direct kernel does not take), direct (k_gram_direct,
+ *                                   else k_gram), SAME, ALIGNED, k_gram_tail runs, T of k_gram_direct, TPW of k_gram,
+ *                                   waves per SIMD, waves, partial Grams, rows in whole pipeline steps, LDS bytes}
+ *   kind 1, the symmetric pair (k_gram_pair_sym): in = {m, k, both Grams in one launch (0: the generalized problem),
+ *                                   NO_GRAM_HALF, compute units};  out = {T, HALF, PAIR, waves per SIMD, waves, rows in
+ *                                   whole 16-row steps}
+ *   kind 2, the eligibility rule of those kernels: in = {m, k, every column block 32-byte aligned, least row count};
+ *                                   out = {eligible, least row count of k_gram_direct, of k_gram_pair_sym} */
+MI_API int mi_debug_lobpcg_gram_plan(int kind, const size_t *in, size_t *out);
+/* host-only: the plan of Y = S C for a basis of nblocks column blocks (cols[i] columns each) and kc output columns, and
+ * the packed coefficients Ct of the column-major C (ks x kc, leading dimension ldc) as the kernels read them.
+ *   all_mfma: the matrix-pipe kernel runs;  steps: nsteps x {block, first column within it, basis column behind each of
+ *   the four coefficient rows or -1}, room for 18;  chunks: nchunks x {first output column, width, offset in Ct}, room
+ *   for 4;  Ct: ct_len doubles, room for ct_cap */
+MI_API int mi_debug_lobpcg_update_plan(size_t m, int kc, int nblocks, const int *cols, int no_update_mfma,
+                                       const double *C_host, int ldc, int *all_mfma, int *nsteps, int *steps,
+                                       int *nchunks, int *chunks, double *Ct, size_t ct_cap, size_t *ct_len);
+/* host-only: the grid of the plane-sweep panel product for a far stride of D rows, n rows, k columns and SWEEP_ZSEGS
+ * (0: chosen here): out = {the form takes this D (else the window form runs), tiles per plane, planes, passes, z-segments,
+ * planes per segment, workgroups per pass} */
+MI_API int mi_debug_lobpcg_sweep_plan(size_t D, size_t n, int k, int num_cu, int sweep_zsegs, int out[7]);
 /* host-only: Config::words16 of a context created with MI355OPT_WORDS16 = text (NULL: unset); needs no GPU */
 MI_API int mi_debug_words16_option(const char *text, int *on);
 MI_API int mi_debug_set_rank(mi_ctx *ctx, int world_size, int rank);

@@ -327,25 +327,38 @@ def build_sanitize(force=False, run=True):
     # (a tree that carries another version of tests/ may not have the packer's program: it has no test of it either)
     if os.path.exists(os.path.join(tdir, "sanitize_so3_pack.cpp")):
         build_sanitize_so3_pack(force=force, run=run)
+    if os.path.exists(os.path.join(tdir, "sanitize_lobpcg_plan.cpp")):
+        build_sanitize_lobpcg_plan(force=force, run=run)
     return exe
 
 
-def build_sanitize_so3_pack(force=False, run=True):
-    """tests/cpp/sanitize_so3_pack: the host-side layout of an SO(3)^N problem (csrc/so3_pack.h) with its failure paths,
-    on its own under the same sanitizers; built and run by build_sanitize() and by tests/test_cpu_so3n_pack.py."""
+def _sanitize_header(name, header, force, run):
+    """tests/cpp/<name>.cpp, a main over the host-only csrc/<header>, built and run on its own under the sanitizers"""
     tdir = os.path.join(ROOT, "tests", "cpp")
-    exe, src = os.path.join(tdir, "sanitize_so3_pack"), os.path.join(tdir, "sanitize_so3_pack.cpp")
+    exe, src = os.path.join(tdir, name), os.path.join(tdir, name + ".cpp")
     asan_opts = _sanitizer_probe(tdir, _SAN)
-    if force or _newer(src, exe, [os.path.join(CSRC, "so3_pack.h")]):
+    if force or _newer(src, exe, [os.path.join(CSRC, header)]):
         r = subprocess.run(["g++", "-std=c++17", "-Wall"] + _SAN + ["-I", CSRC, src, "-o", exe], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("sanitizer build failed:\n" + r.stderr[-6000:])
     if run:
         r = subprocess.run([exe], capture_output=True, text=True, timeout=600,
                            env=dict(os.environ, ASAN_OPTIONS=asan_opts, UBSAN_OPTIONS="print_stacktrace=1"))
-        if r.returncode != 0 or "sanitize_so3_pack: ok" not in r.stdout:
-            raise RuntimeError("so3_pack.h failed under ASan/UBSan:\n" + r.stdout[-2000:] + r.stderr[-6000:])
+        if r.returncode != 0 or name + ": ok" not in r.stdout:
+            raise RuntimeError(header + " failed under ASan/UBSan:\n" + r.stdout[-2000:] + r.stderr[-6000:])
     return exe
+
+
+def build_sanitize_so3_pack(force=False, run=True):
+    """tests/cpp/sanitize_so3_pack: the host-side layout of an SO(3)^N problem (csrc/so3_pack.h) with its failure paths,
+    on its own under the same sanitizers; built and run by build_sanitize() and by tests/test_cpu_so3n_pack.py."""
+    return _sanitize_header("sanitize_so3_pack", "so3_pack.h", force, run)
+
+
+def build_sanitize_lobpcg_plan(force=False, run=True):
+    """tests/cpp/sanitize_lobpcg_plan: the plans of the LOBPCG host layer (csrc/lobpcg_plan.h) with the shapes they
+    refuse; built and run by build_sanitize() and by tests/test_cpu_lobpcg_plan.py."""
+    return _sanitize_header("sanitize_lobpcg_plan", "lobpcg_plan.h", force, run)
 
 
 if __name__ == "__main__":

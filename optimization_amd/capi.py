@@ -306,6 +306,44 @@ def stiefel_hess_form(p, gram_count, traits, switches):
     return list(out) if st == MI_OK else None
 
 
+def lobpcg_gram_plan_fn():
+    """mi_debug_lobpcg_gram_plan(kind, in, out), bound on first use; the kinds and their numbers are in mi355opt.h"""
+    fn = load().mi_debug_lobpcg_gram_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, c_size_p, c_size_p]
+    return fn
+
+
+def lobpcg_update_plan(m, cols, kc, Cmat, no_update_mfma=False):
+    """plan of Y = S C and the packed coefficients (host-only, mi_debug_lobpcg_update_plan): (all_mfma, steps as rows
+    of [block, first, four basis columns or -1], chunks as rows of [c0, width, offset], Ct).  Cmat: Fortran-ordered,
+    at least sum(cols) rows (its leading dimension may be larger), kc columns."""
+    fn = load().mi_debug_lobpcg_update_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, c_double_p, C.c_int, C.POINTER(C.c_int),
+                   C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p,
+                   C.c_size_t, c_size_p]
+    assert Cmat.flags.f_contiguous and Cmat.dtype == np.float64 and Cmat.shape[1] >= kc
+    cap = 96 * 96 * 2
+    mf, ns, nc, n = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    steps, chunks, Ct = (C.c_int * (18 * 6))(), (C.c_int * 12)(), np.full(cap, np.nan)
+    check(fn(m, kc, len(cols), (C.c_int * len(cols))(*cols), int(no_update_mfma), Cmat.ctypes.data_as(c_double_p),
+             Cmat.shape[0], C.byref(mf), C.byref(ns), steps, C.byref(nc), chunks, Ct.ctypes.data_as(c_double_p), cap,
+             C.byref(n)))
+    return (bool(mf.value), np.array(steps[:6 * ns.value], dtype=np.int64).reshape(-1, 6),
+            np.array(chunks[:3 * nc.value], dtype=np.int64).reshape(-1, 3), Ct[:n.value].copy())
+
+
+def lobpcg_sweep_plan(D, n, k, num_cu=256, sweep_zsegs=0):
+    """grid of the plane-sweep panel product (host-only, mi_debug_lobpcg_sweep_plan): dict of the 7 numbers of `out`"""
+    fn = load().mi_debug_lobpcg_sweep_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    out = (C.c_int * 7)()
+    check(fn(D, n, k, num_cu, sweep_zsegs, out))
+    return dict(zip(("ok", "tiles", "nst", "npass", "zsegs", "zs", "xgrid"), out))
+
+
 def words16_option(text=None):
     """mi_debug_words16_option (host-only): Config::words16 of a context created with MI355OPT_WORDS16=text (None: unset)"""
     fn = load().mi_debug_words16_option

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "lobpcg_plan.h"
 #include "mi_internal.h"
 #include "spmm_core.h"
 
@@ -1355,8 +1356,24 @@ int check_panel(mi_ctx *ctx, size_t m, int k, const mi_vec *P, const char *what)
 
 extern "C" {
 
+// Host half.  Every decision -- which kernel, which template arguments, what grid, how C is packed -- is made in
+// lobpcg_plan.h (host-only, pinned by tests/test_cpu_lobpcg_plan.py); the code below validates, allocates and launches.
+// Every buffer has an owner (mi_internal.h: PoolBuf, Owned<mi_vec>), so an early return releases what was made so far.
+static_assert(kPlanGramRows == kGramRows && kPlanGramLd == kGramLd && kPlanGramWaves == kGramWaves && kPlanGdH == kGdH &&
+                  kPlanSwRows == kSwRows && kPlanMaxRows == kMaxRows &&
+                  kPlanMaxSteps == sizeof(StepBases) / sizeof(const double *),
+              "lobpcg_plan.h plans for the kernels of this file");
+
 // ---- panels held as column blocks (mi_panel_blocks, include/mi355opt.h) ----------------------------------------------
 static ColBlocks one_block(const double *d, int k) { return ColBlocks{{d, d, d}, k, k}; }
+// T = [T1 (k1 columns) | T2] of k columns; T2 == null: T1 alone, k1 == k
+static ColBlocks two_blocks(int k, int k1, const mi_vec *T1, const mi_vec *T2) {
+  const double *t2 = T2 ? T2->d : T1->d;
+  return ColBlocks{{T1->d, t2, t2}, k1, k};
+}
+static bool aligned32(const ColBlocks &c) {
+  return aligned_to(32, {(uintptr_t)c.base[0], (uintptr_t)c.base[1], (uintptr_t)c.base[2]});
+}
 // validated kernel-side description of a mi_panel_blocks and its total width
 static int blocks_to_cols(mi_ctx *ctx, size_t m, const mi_panel_blocks *B, ColBlocks *cb, int *k) {
   MI_REQUIRE(B && B->nblocks >= 1 && B->nblocks <= 3, "a panel has 1 to 3 column blocks");
@@ -1375,47 +1392,58 @@ static int blocks_to_cols(mi_ctx *ctx, size_t m, const mi_panel_blocks *B, ColBl
   *k = total;
   return MI_OK;
 }
-// the blocks copied together into one panel (the fall-back of every *_blocks entry point whose fast kernel does not
-// take the shape at hand); the caller destroys *out
-static int materialize_blocks(mi_ctx *ctx, size_t m, const mi_panel_blocks *B, mi_vec **out) {
-  int k = 0;
-  for (int i = 0; i < B->nblocks; ++i) k += B->cols[i];
-  MI_TRY(mi_vec_create(ctx, m * (size_t)k, out));
-  size_t off = 0;
-  for (int i = 0; i < B->nblocks; ++i) {
-    const size_t cnt = m * (size_t)B->cols[i];
-    const hipError_t e = hipMemcpyAsync((*out)->d + off, B->block[i]->d, cnt * sizeof(double), hipMemcpyDeviceToDevice,
-                                        ctx->stream);
-    if (e != hipSuccess) {
-      mi_vec_destroy(*out);
-      *out = nullptr;
-      return hip_fail(e, "panel blocks copy", __FILE__, __LINE__);
-    }
-    off += cnt;
+// out = the pieces (cnt[i] doubles each) copied together into one fresh panel; out is left as it was on failure
+static int join_pieces(mi_ctx *ctx, int n, const mi_vec *const *piece, const size_t *cnt, const char *what,
+                       Owned<mi_vec> &out) {
+  size_t total = 0, off = 0;
+  for (int i = 0; i < n; ++i) total += cnt[i];
+  Owned<mi_vec> v;
+  MI_TRY(vec_alloc(ctx, total, v));
+  for (int i = 0; i < n; off += cnt[i++]) {
+    const hipError_t e =
+        hipMemcpyAsync(v->d + off, piece[i]->d, cnt[i] * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
   }
+  out = std::move(v);
   return MI_OK;
 }
+// the blocks copied together into one panel (the fall-back of every *_blocks entry point whose fast kernel does not
+// take the shape at hand)
+static int materialize_blocks(mi_ctx *ctx, size_t m, const mi_panel_blocks *B, Owned<mi_vec> &out) {
+  size_t cnt[3];
+  for (int i = 0; i < B->nblocks; ++i) cnt[i] = m * (size_t)B->cols[i];
+  return join_pieces(ctx, B->nblocks, B->block, cnt, "panel blocks copy", out);
+}
+// T = [T1 | T2] assembled in a fresh panel (for shapes the split kernel does not take)
+static int assemble_panel(mi_ctx *ctx, size_t m, int k, int k1, const mi_vec *T1, const mi_vec *T2, Owned<mi_vec> &out) {
+  const mi_vec *piece[2] = {T1, T2};
+  const size_t cnt[2] = {m * (size_t)k1, m * (size_t)(k - k1)};
+  return join_pieces(ctx, 2, piece, cnt, "panel assembly", out);
+}
 
-// a Gram whose kernels are enqueued but whose result has not been read back yet (gram_impl with job != null)
+// A Gram whose kernels are enqueued but whose result has not been read back yet.  The buffers go back to the pool when
+// the job dies, read back or not: pool reuse is stream-ordered, later allocations are enqueued after these kernels.
 struct GramJob {
-  void *partial = nullptr, *Gdev = nullptr;
+  PoolBuf partial, Gbuf;  // the per-wave / per-workgroup partial Grams; the reduced Gram (empty: G is a zero-copy slot)
+  double *G = nullptr;
   int nelem = 0;
 };
-static int gram_finish(mi_ctx *ctx, GramJob *jobs, int njobs, double *const *G_host) {
+static int gram_finish(mi_ctx *ctx, const GramJob *jobs, int njobs, double *const *G_host) {
   const void *dev[4];
   size_t bytes[4];
   void *host[4];
   for (int i = 0; i < njobs && i < 4; ++i) {
-    dev[i] = jobs[i].Gdev;
+    dev[i] = jobs[i].G;
     bytes[i] = (size_t)jobs[i].nelem * sizeof(double);
     host[i] = G_host[i];
   }
-  const int st = njobs > 0 ? readback_sync(ctx, njobs, dev, bytes, host) : MI_OK;  // (pinned landing area: no blit kernel)
-  for (int i = 0; i < njobs; ++i) {
-    pool_free(ctx, jobs[i].partial);
-    pool_free(ctx, jobs[i].Gdev);
-  }
-  return st;
+  return njobs > 0 ? readback_sync(ctx, njobs, dev, bytes, host) : MI_OK;  // (pinned landing area: no blit kernel)
+}
+static int gram_allreduce(mi_ctx *ctx, const GramJob &job) {
+  if (ctx->comm)
+    for (int off = 0; off < job.nelem; off += 4096)  // all-reduce in chunks the comm layer accepts
+      MI_TRY(comm_allreduce(ctx, job.G + off, std::min(4096, job.nelem - off)));
+  return MI_OK;
 }
 
 // T = [T (k1 columns) | T2 (kb - k1 columns)] when T2 != null (square direct shapes only), else T alone.
@@ -1423,118 +1451,67 @@ static int gram_finish(mi_ctx *ctx, GramJob *jobs, int njobs, double *const *G_h
 static int gram_impl(mi_ctx *ctx, size_t m, int ka, int kb, const mi_vec *S, const mi_vec *T, const mi_vec *T2v,
                      int k1, double *G_host, GramJob *job = nullptr) {
   const double *T2 = T2v ? T2v->d : nullptr;
-  const bool same = !T2 && (S->d == T->d) && ka == kb;
-  const bool aligned = (m % 2 == 0) && ((uintptr_t)S->d % 16 == 0) && ((uintptr_t)T->d % 16 == 0);
-  const int nelem = ka * kb;
-  const int kapad = (ka + 15) / 16 * 16, kbpad = (kb + 15) / 16 * 16;
-  // square panels of up to 80 columns on 32-byte-aligned columns: the LDS-free one-wave-per-row-range kernel
-  const bool direct = ka == kb && ka <= 80 && m % 4 == 0 && (uintptr_t)S->d % 32 == 0 && (uintptr_t)T->d % 32 == 0 &&
-                      (!T2 || (uintptr_t)T2 % 32 == 0) && m >= 16 * kGdH;
-  MI_REQUIRE(!T2 || direct, "split panels need the direct Gram kernel");
-  size_t nb, nwaves = 0;
-  const size_t mfull = m - m % (16 * kGdH);  // rows k_gram_direct covers in whole pipeline steps
-  if (direct) {  // one partial per wave + one for the leftover rows
-    // two waves per SIMD where the registers allow it (k <= 48, and k <= 80 when S == T), else one
-    const int occ = (kapad <= 48 || same) ? 2 : 1;
-    nwaves = (std::min<size_t>(4 * (size_t)occ * ctx->num_cu, mfull / (16 * kGdH)) + 3) / 4 * 4;
-    nb = nwaves + (mfull < m ? 1 : 0);
-  } else {  // rows per workgroup: a multiple of the 32-row tile, ~3 workgroups per CU
-    nb = std::min<size_t>(3 * (size_t)ctx->num_cu, (m + kGramRows - 1) / kGramRows);
-    if (nb < 1) nb = 1;
-  }
-  void *partial = nullptr, *Gdev = nullptr;
-  MI_TRY(pool_alloc(ctx, nb * (size_t)nelem * sizeof(double), &partial));
-  MI_TRY(pool_alloc(ctx, (size_t)nelem * sizeof(double), &Gdev));
-  const size_t lds = (size_t)(same ? kapad : kapad + kbpad) * kGramLd * sizeof(double);
-  if (direct) {
+  const uintptr_t s = (uintptr_t)S->d, t = (uintptr_t)T->d;
+  const GramPlan p = gram_plan(m, ka, kb, S->d == T->d, T2 != nullptr, aligned_to(16, {s, t}),
+                               aligned_to(32, {s, t, (uintptr_t)T2}), ctx->num_cu);
+  MI_REQUIRE(p.ok, "split panels need the direct Gram kernel");
+  GramJob mine;
+  const int nelem = mine.nelem = ka * kb;
+  MI_TRY(mine.partial.alloc(ctx, p.nb * (size_t)nelem * sizeof(double)));
+  MI_TRY(mine.Gbuf.alloc(ctx, (size_t)nelem * sizeof(double)));
+  mine.G = mine.Gbuf.doubles();
+  double *partial = mine.partial.doubles();
+  {
     KScope ks(ctx, MI_K_LOBPCG_GRAM);
-    if (mfull < m)
-      hipLaunchKernelGGL(k_gram_tail, dim3((nelem + 255) / 256), dim3(256), 0, ctx->stream, m, mfull, ka, kb,
-                         (const double *)S->d, (const double *)T->d, T2, k1,
-                         (double *)partial + (nb - 1) * (size_t)nelem);
-#define GD(TT, SAME, NS)                                                                                  \
-  hipLaunchKernelGGL((k_gram_direct<TT, SAME>), dim3((unsigned)(nwaves / 4)), dim3(256), 0, ctx->stream, \
-                     mfull, m, ka, (const double *)S->d, (const double *)T->d, T2, k1, (double *)partial)
-#define GD_T(SAME)                   \
-  switch (kapad / 16) {              \
-    case 1: GD(1, SAME, 1); break;   \
-    case 2: GD(2, SAME, 1); break;   \
-    case 3: GD(3, SAME, 1); break;   \
-    case 4: GD(4, SAME, 1); break;   \
-    default: GD(5, SAME, 1); break;  \
-  }
-    if (same) {
-      GD_T(true)
+    if (p.direct) {  // one partial per wave + one for the leftover rows
+      if (p.tail)
+        hipLaunchKernelGGL(k_gram_tail, dim3((nelem + 255) / 256), dim3(256), 0, ctx->stream, m, p.mfull, ka, kb, S->d,
+                           T->d, T2, k1, partial + (p.nb - 1) * (size_t)nelem);
+      dispatch_int<1, 5>(p.T, [&](auto tt) {
+        constexpr int TT = decltype(tt)::value;
+        auto fn = p.same ? k_gram_direct<TT, true> : k_gram_direct<TT, false>;
+        hipLaunchKernelGGL(fn, dim3((unsigned)(p.nwaves / 4)), dim3(256), 0, ctx->stream, p.mfull, m, ka, S->d, T->d, T2,
+                           k1, partial);
+      });
     } else {
-      GD_T(false)
+      dispatch_int<1, 5>(p.tpw, [&](auto tw) {
+        constexpr int TPW = decltype(tw)::value;
+        auto fn = p.same ? (p.aligned ? k_gram<true, true, TPW> : k_gram<true, false, TPW>)
+                         : (p.aligned ? k_gram<false, true, TPW> : k_gram<false, false, TPW>);
+        hipLaunchKernelGGL(fn, dim3((unsigned)p.nb), dim3(kGramThreads), p.lds, ctx->stream, m, ka, kb, S->d, T->d,
+                           partial);
+      });
     }
-#undef GD_T
-#undef GD
-  } else {
-    KScope ks(ctx, MI_K_LOBPCG_GRAM);
-    const int ta = kapad / 16, tb = kbpad / 16;
-    const int ntiles = same ? ta * (ta + 1) / 2 : ta * tb;
-    const int tpw = (ntiles + kGramWaves - 1) / kGramWaves;  // 1..5
-#define GRAM(SAME, AL, TPW)                                                                                        \
-  hipLaunchKernelGGL((k_gram<SAME, AL, TPW>), dim3((unsigned)nb), dim3(kGramThreads), lds, ctx->stream, m, ka, kb, \
-                     (const double *)S->d, (const double *)T->d, (double *)partial)
-#define GRAM_T(SAME, AL)        \
-  switch (tpw) {                \
-    case 1: GRAM(SAME, AL, 1); break; \
-    case 2: GRAM(SAME, AL, 2); break; \
-    case 3: GRAM(SAME, AL, 3); break; \
-    case 4: GRAM(SAME, AL, 4); break; \
-    default: GRAM(SAME, AL, 5); break; \
-  }
-    if (same) {
-      if (aligned) {
-        GRAM_T(true, true)
-      } else {
-        GRAM_T(true, false)
-      }
-    } else {
-      if (aligned) {
-        GRAM_T(false, true)
-      } else {
-        GRAM_T(false, false)
-      }
-    }
-#undef GRAM_T
-#undef GRAM
   }
   hipLaunchKernelGGL(k_gram_reduce, dim3((nelem + kRedElems - 1) / kRedElems), dim3(kRedElems * kRedGroups), 0,
-                     ctx->stream, (int)nb, ka, nelem, (int)same, (const double *)partial, (double *)Gdev);
-  if (ctx->comm) {
-    for (int off = 0; off < nelem; off += 4096)  // all-reduce in chunks the comm layer accepts
-      MI_TRY(comm_allreduce(ctx, (double *)Gdev + off, std::min(4096, nelem - off)));
-  }
-  GramJob mine{partial, Gdev, nelem};
+                     ctx->stream, (int)p.nb, ka, nelem, (int)p.same, partial, mine.G);
+  MI_TRY(gram_allreduce(ctx, mine));
   if (job) {
-    *job = mine;
+    *job = std::move(mine);
     return MI_OK;
   }
   double *dst[1] = {G_host};
   return gram_finish(ctx, &mine, 1, dst);
 }
 
-// assembles T = [T1 | T2] in a fresh panel (for shapes the split kernel does not take)
-static int assemble_panel(mi_ctx *ctx, size_t m, int k, int k1, const mi_vec *T1, const mi_vec *T2, mi_vec **out) {
-  MI_TRY(mi_vec_create(ctx, m * (size_t)k, out));
-  hipError_t e = hipMemcpyAsync((*out)->d, T1->d, m * (size_t)k1 * sizeof(double), hipMemcpyDeviceToDevice,
-                                ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync((*out)->d + m * (size_t)k1, T2->d, m * (size_t)(k - k1) * sizeof(double),
-                       hipMemcpyDeviceToDevice, ctx->stream);
-  if (e != hipSuccess) {
-    mi_vec_destroy(*out);
-    *out = nullptr;
-    return hip_fail(e, "panel assembly", __FILE__, __LINE__);
-  }
-  return MI_OK;
-}
+// k_gram_direct takes the two pieces of T = [T1 | T2] as they lie
 static bool split_direct_ok(size_t m, int k, const mi_vec *S, const mi_vec *T1, const mi_vec *T2) {
-  return k <= 80 && m % 4 == 0 && (uintptr_t)S->d % 32 == 0 && (uintptr_t)T1->d % 32 == 0 &&
-         (uintptr_t)T2->d % 32 == 0 && m >= 16 * kGdH;
+  return gram_direct_ok(m, k, aligned_to(32, {(uintptr_t)S->d, (uintptr_t)T1->d, (uintptr_t)T2->d}), kGramDirectMinRows);
+}
+// one Gram of mi_lobpcg_gram_pair / mi_lobpcg_gram_split enqueued: T = T1 of k columns (T2 == null) or [T1 | T2];
+// tmp keeps the assembled T alive where the split kernel does not take the shape
+static int gram_enqueue(mi_ctx *ctx, size_t m, int k, const mi_vec *S, int k1, const mi_vec *T1, const mi_vec *T2,
+                        Owned<mi_vec> &tmp, GramJob *job) {
+  if (!T2) {
+    MI_TRY(check_panel(ctx, m, k, T1, "T"));
+    return gram_impl(ctx, m, k, k, S, T1, nullptr, k, nullptr, job);
+  }
+  MI_REQUIRE(k1 >= 1 && k1 < k, "need 1 <= k1 < k");
+  MI_TRY(check_panel(ctx, m, k1, T1, "T1"));
+  MI_TRY(check_panel(ctx, m, k - k1, T2, "T2"));
+  if (split_direct_ok(m, k, S, T1, T2)) return gram_impl(ctx, m, k, k, S, T1, T2, k1, nullptr, job);
+  MI_TRY(assemble_panel(ctx, m, k, k1, T1, T2, tmp));
+  return gram_impl(ctx, m, k, k, S, tmp.get(), nullptr, k, nullptr, job);
 }
 
 // The two Grams of a Rayleigh-Ritz step with ONE synchronisation: both are enqueued back to back (the device goes
@@ -1545,83 +1522,111 @@ int mi_lobpcg_gram_pair(mi_ctx *ctx, size_t m, int k, const mi_vec *S, int k1a, 
   MI_REQUIRE(ctx && S && Ta1 && Tb1 && Ga_host && Gb_host, "null argument");
   MI_REQUIRE(k >= 1 && k <= kGramMaxK, "panel width must be in [1,%d]", kGramMaxK);
   MI_TRY(check_panel(ctx, m, k, S, "S"));
-  const mi_vec *T1[2] = {Ta1, Tb1}, *T2[2] = {Ta2, Tb2};
-  const int k1[2] = {k1a, k1b};
   GramJob jobs[2];
-  mi_vec *tmp[2] = {nullptr, nullptr};
-  int st = MI_OK, started = 0;
-  for (int i = 0; i < 2 && st == MI_OK; ++i) {
-    if (T2[i]) {
-      if (!(k1[i] >= 1 && k1[i] < k)) { set_error("need 1 <= k1 < k"); st = MI_ERR_INVALID_ARGUMENT; break; }
-      st = check_panel(ctx, m, k1[i], T1[i], "T1");
-      if (st == MI_OK) st = check_panel(ctx, m, k - k1[i], T2[i], "T2");
-      if (st != MI_OK) break;
-      if (split_direct_ok(m, k, S, T1[i], T2[i])) {
-        st = gram_impl(ctx, m, k, k, S, T1[i], T2[i], k1[i], nullptr, &jobs[i]);
-      } else {
-        st = assemble_panel(ctx, m, k, k1[i], T1[i], T2[i], &tmp[i]);
-        if (st == MI_OK) st = gram_impl(ctx, m, k, k, S, tmp[i], nullptr, k, nullptr, &jobs[i]);
-      }
-    } else {
-      st = check_panel(ctx, m, k, T1[i], "T");
-      if (st == MI_OK) st = gram_impl(ctx, m, k, k, S, T1[i], nullptr, k, nullptr, &jobs[i]);
-    }
-    if (st == MI_OK) ++started;
-  }
+  Owned<mi_vec> tmp[2];
+  MI_TRY(gram_enqueue(ctx, m, k, S, k1a, Ta1, Ta2, tmp[0], &jobs[0]));
+  MI_TRY(gram_enqueue(ctx, m, k, S, k1b, Tb1, Tb2, tmp[1], &jobs[1]));
   double *dst[2] = {Ga_host, Gb_host};
-  const int fin = gram_finish(ctx, jobs, started, dst);  // (also releases what was enqueued when a later step failed)
-  for (int i = 0; i < 2; ++i) mi_vec_destroy(tmp[i]);
-  return st != MI_OK ? st : fin;
+  return gram_finish(ctx, jobs, 2, dst);
+}
+
+// k_gram_pair_sym takes S, TA and (generalized problem) TB as they lie
+static bool gram_pair_direct_ok(size_t m, int k, const ColBlocks &S, const ColBlocks &TA, const ColBlocks *TB) {
+  return gram_direct_ok(m, k, aligned32(S) && aligned32(TA) && (!TB || aligned32(*TB)), kGramPairMinRows);
+}
+
+// Upper block triangles of S'TA and of S'S (TB == null: both from one launch of k_gram_pair_sym<., HALF, PAIR = true>)
+// or of S'TA and S'TB (the generalized problem, TA = A(S), TB = B(S): one launch of k_gram_pair_sym<., false, false>
+// each); one reduction launch, one synchronisation.  Arguments validated by the callers.
+static int gram_pair_sym_direct(mi_ctx *ctx, size_t m, int k, const ColBlocks &S, const ColBlocks &TA,
+                                const ColBlocks *TB, double *Ga_host, double *Gb_host) {
+  const GramPairPlan p = gram_pair_plan(m, k, TB == nullptr, ctx->cfg.no_gram_half, ctx->num_cu);
+  const int nelem = k * k;
+  // One rank: the reduction kernel writes the two k x k results STRAIGHT into pinned host memory (82 KB over PCIe at
+  // ns = 72) -- no device buffer, no copy behind the kernel (a blit kernel of ~15 us per Gram even into pinned memory).
+  // Several ranks: the results are all-reduced on the device first.
+  const bool zero_copy = ctx->comm == nullptr && !ctx->cfg.no_zero_copy;
+  const size_t slot = ((size_t)nelem * sizeof(double) + 255) / 256 * 256;
+  char *zc_host = nullptr, *zc_dev = nullptr;
+  if (zero_copy) MI_TRY(readback_area(ctx, 2 * slot, (void **)&zc_host, (void **)&zc_dev));
+  GramJob jobs[2];
+  for (int i = 0; i < 2; ++i) {
+    jobs[i].nelem = nelem;
+    MI_TRY(jobs[i].partial.alloc(ctx, p.nwaves * (size_t)nelem * sizeof(double)));
+    if (!zero_copy) MI_TRY(jobs[i].Gbuf.alloc(ctx, (size_t)nelem * sizeof(double)));
+    jobs[i].G = zero_copy ? (double *)(zc_dev + (size_t)i * slot) : jobs[i].Gbuf.doubles();
+  }
+  double *pa = jobs[0].partial.doubles(), *pb = jobs[1].partial.doubles();
+  {
+    KScope ks(ctx, MI_K_LOBPCG_GRAM);
+    const dim3 grid((unsigned)(p.nwaves / 4));
+    dispatch_int<1, 5>(p.T, [&](auto tt) {
+      constexpr int TT = decltype(tt)::value;
+      if (p.pair) {
+        auto fn = p.half ? k_gram_pair_sym<TT, true, true> : k_gram_pair_sym<TT, false, true>;
+        hipLaunchKernelGGL(fn, grid, dim3(256), 0, ctx->stream, p.mfull, m, k, S, TA, pa, pb);
+      } else {
+        hipLaunchKernelGGL((k_gram_pair_sym<TT, false, false>), grid, dim3(256), 0, ctx->stream, p.mfull, m, k, S, TA,
+                           pa, (double *)nullptr);
+        hipLaunchKernelGGL((k_gram_pair_sym<TT, false, false>), grid, dim3(256), 0, ctx->stream, p.mfull, m, k, S, *TB,
+                           pb, (double *)nullptr);
+      }
+    });
+  }
+  hipLaunchKernelGGL(k_gram_reduce, dim3((nelem + kRedElems - 1) / kRedElems, 2), dim3(kRedElems * kRedGroups), 0,
+                     ctx->stream, (int)p.nwaves, k, nelem, 1, pa, jobs[0].G, pb, jobs[1].G);
+  MI_TRY(gram_allreduce(ctx, jobs[0]));
+  MI_TRY(gram_allreduce(ctx, jobs[1]));
+  double *dst[2] = {Ga_host, Gb_host};
+  if (zero_copy) {
+    MI_TRY(stream_wait(ctx, "gram read-back"));
+    for (int i = 0; i < 2; ++i) memcpy(dst[i], zc_host + (size_t)i * slot, (size_t)nelem * sizeof(double));
+  } else {
+    MI_TRY(gram_finish(ctx, jobs, 2, dst));
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MI_OK : hip_fail(e, "symmetric Gram pair launch", __FILE__, __LINE__);
+}
+
+// the checks mi_lobpcg_gram_pair_sym and its _blocks form share: T = Ta1 of k columns or [Ta1 (k1a columns) | Ta2]
+static int check_split(mi_ctx *ctx, size_t m, int k, int *k1a, const mi_vec *Ta1, const mi_vec *Ta2) {
+  if (Ta2) {
+    MI_REQUIRE(*k1a >= 1 && *k1a < k, "need 1 <= k1 < k");
+    MI_TRY(check_panel(ctx, m, *k1a, Ta1, "T1"));
+    return check_panel(ctx, m, k - *k1a, Ta2, "T2");
+  }
+  *k1a = k;
+  return check_panel(ctx, m, k, Ta1, "T");
 }
 
 // G_A = S' [Ta1 | Ta2] for a SYMMETRIC product (T = A S with a symmetric operator: G_A is symmetric and only its upper
 // block triangle is formed, the mirror image filled in) and G_B = S' S, both from ONE pass over S and T
 // (k_gram_pair_sym); one synchronisation.  Ta2 may be null (one panel of k columns).  Shapes the fused kernel does not
 // take (k > 80, unaligned panels, fewer than 16 rows) go through mi_lobpcg_gram_pair, which forms all of G_A.
-static bool gram_pair_sym_direct_ok(size_t m, int k, const ColBlocks &S, const mi_vec *Ta1, const mi_vec *Ta2);
-static int gram_pair_sym_direct(mi_ctx *ctx, size_t m, int k, const ColBlocks &Sb, int k1a, const mi_vec *Ta1,
-                                const mi_vec *Ta2, double *Ga_host, double *Gb_host,
-                                const ColBlocks *Tab = nullptr, const ColBlocks *Tbb = nullptr);
-
 int mi_lobpcg_gram_pair_sym(mi_ctx *ctx, size_t m, int k, const mi_vec *S, int k1a, const mi_vec *Ta1,
                             const mi_vec *Ta2, double *Ga_host, double *Gb_host) {
   MI_REQUIRE(ctx && S && Ta1 && Ga_host && Gb_host, "null argument");
   MI_REQUIRE(k >= 1 && k <= kGramMaxK, "panel width must be in [1,%d]", kGramMaxK);
   MI_TRY(check_panel(ctx, m, k, S, "S"));
-  if (Ta2) {
-    MI_REQUIRE(k1a >= 1 && k1a < k, "need 1 <= k1 < k");
-    MI_TRY(check_panel(ctx, m, k1a, Ta1, "T1"));
-    MI_TRY(check_panel(ctx, m, k - k1a, Ta2, "T2"));
-  } else {
-    MI_TRY(check_panel(ctx, m, k, Ta1, "T"));
-    k1a = k;
-  }
-  if (!gram_pair_sym_direct_ok(m, k, one_block(S->d, k), Ta1, Ta2))
+  MI_TRY(check_split(ctx, m, k, &k1a, Ta1, Ta2));
+  const ColBlocks cs = one_block(S->d, k), ta = two_blocks(k, k1a, Ta1, Ta2);
+  if (!gram_pair_direct_ok(m, k, cs, ta, nullptr))
     return mi_lobpcg_gram_pair(ctx, m, k, S, k1a, Ta1, Ta2, k, S, nullptr, Ga_host, Gb_host);
-  return gram_pair_sym_direct(ctx, m, k, one_block(S->d, k), k1a, Ta1, Ta2, Ga_host, Gb_host);
+  return gram_pair_sym_direct(ctx, m, k, cs, ta, nullptr, Ga_host, Gb_host);
 }
 
 int mi_lobpcg_gram_pair_sym_blocks(mi_ctx *ctx, size_t m, const mi_panel_blocks *S, int k1a, const mi_vec *Ta1,
                                    const mi_vec *Ta2, double *Ga_host, double *Gb_host) {
   MI_REQUIRE(ctx && S && Ta1 && Ga_host && Gb_host, "null argument");
-  ColBlocks cb;
+  ColBlocks cs;
   int k = 0;
-  MI_TRY(blocks_to_cols(ctx, m, S, &cb, &k));
-  if (Ta2) {
-    MI_REQUIRE(k1a >= 1 && k1a < k, "need 1 <= k1 < k");
-    MI_TRY(check_panel(ctx, m, k1a, Ta1, "T1"));
-    MI_TRY(check_panel(ctx, m, k - k1a, Ta2, "T2"));
-  } else {
-    MI_TRY(check_panel(ctx, m, k, Ta1, "T"));
-    k1a = k;
-  }
-  if (gram_pair_sym_direct_ok(m, k, cb, Ta1, Ta2))
-    return gram_pair_sym_direct(ctx, m, k, cb, k1a, Ta1, Ta2, Ga_host, Gb_host);
-  mi_vec *tmp = nullptr;  // shapes the one-pass kernel does not take: the blocks copied together, the general path
-  MI_TRY(materialize_blocks(ctx, m, S, &tmp));
-  const int st = mi_lobpcg_gram_pair_sym(ctx, m, k, tmp, k1a, Ta1, Ta2, Ga_host, Gb_host);
-  mi_vec_destroy(tmp);
-  return st;
+  MI_TRY(blocks_to_cols(ctx, m, S, &cs, &k));
+  MI_TRY(check_split(ctx, m, k, &k1a, Ta1, Ta2));
+  const ColBlocks ta = two_blocks(k, k1a, Ta1, Ta2);
+  if (gram_pair_direct_ok(m, k, cs, ta, nullptr)) return gram_pair_sym_direct(ctx, m, k, cs, ta, nullptr, Ga_host, Gb_host);
+  Owned<mi_vec> s;  // shapes the one-pass kernel does not take: the blocks copied together, the general path
+  MI_TRY(materialize_blocks(ctx, m, S, s));
+  return mi_lobpcg_gram_pair_sym(ctx, m, k, s.get(), k1a, Ta1, Ta2, Ga_host, Gb_host);
 }
 
 // (S'A(S), S'S) like mi_lobpcg_gram_pair_sym_blocks with T = A(S) held as column blocks too: what a plain-callable
@@ -1634,18 +1639,11 @@ int mi_lobpcg_gram_pair_sym_tblocks(mi_ctx *ctx, size_t m, const mi_panel_blocks
   MI_TRY(blocks_to_cols(ctx, m, S, &cs, &k));
   MI_TRY(blocks_to_cols(ctx, m, T, &ct, &kt));
   MI_REQUIRE(kt == k, "A(S) must have the width of S (%d): got %d", k, kt);
-  auto aligned = [](const ColBlocks &c) {
-    return (uintptr_t)c.base[0] % 32 == 0 && (uintptr_t)c.base[1] % 32 == 0 && (uintptr_t)c.base[2] % 32 == 0;
-  };
-  if (k <= 80 && m % 4 == 0 && m >= 16 && aligned(cs) && aligned(ct))
-    return gram_pair_sym_direct(ctx, m, k, cs, k, nullptr, nullptr, Ga_host, Gb_host, &ct, nullptr);
-  mi_vec *s = nullptr, *t = nullptr;
-  int st = materialize_blocks(ctx, m, S, &s);
-  if (st == MI_OK) st = materialize_blocks(ctx, m, T, &t);
-  if (st == MI_OK) st = mi_lobpcg_gram_pair_sym(ctx, m, k, s, k, t, nullptr, Ga_host, Gb_host);
-  mi_vec_destroy(s);
-  mi_vec_destroy(t);
-  return st;
+  if (gram_pair_direct_ok(m, k, cs, ct, nullptr)) return gram_pair_sym_direct(ctx, m, k, cs, ct, nullptr, Ga_host, Gb_host);
+  Owned<mi_vec> s, t;
+  MI_TRY(materialize_blocks(ctx, m, S, s));
+  MI_TRY(materialize_blocks(ctx, m, T, t));
+  return mi_lobpcg_gram_pair_sym(ctx, m, k, s.get(), k, t.get(), nullptr, Ga_host, Gb_host);
 }
 
 // The generalized problem (B present, LOBPCG.h:268,272): upper block triangles of S'A(S) and S'B(S) with S, A(S) and
@@ -1659,124 +1657,13 @@ int mi_lobpcg_gram_pair_gen_blocks(mi_ctx *ctx, size_t m, const mi_panel_blocks 
   MI_TRY(blocks_to_cols(ctx, m, AS, &ca, &ka));
   MI_TRY(blocks_to_cols(ctx, m, BS, &cb, &kb));
   MI_REQUIRE(ka == k && kb == k, "A(S) and B(S) must have the width of S (%d): got %d and %d", k, ka, kb);
-  auto aligned = [](const ColBlocks &c) {
-    return (uintptr_t)c.base[0] % 32 == 0 && (uintptr_t)c.base[1] % 32 == 0 && (uintptr_t)c.base[2] % 32 == 0;
-  };
-  if (k <= 80 && m % 4 == 0 && m >= 16 && aligned(cs) && aligned(ca) && aligned(cb))
-    return gram_pair_sym_direct(ctx, m, k, cs, k, nullptr, nullptr, Ga_host, Gb_host, &ca, &cb);
+  if (gram_pair_direct_ok(m, k, cs, ca, &cb)) return gram_pair_sym_direct(ctx, m, k, cs, ca, &cb, Ga_host, Gb_host);
   // shapes the one-pass kernels do not take: everything copied together, the general pair
-  mi_vec *s = nullptr, *a = nullptr, *b = nullptr;
-  int st = materialize_blocks(ctx, m, S, &s);
-  if (st == MI_OK) st = materialize_blocks(ctx, m, AS, &a);
-  if (st == MI_OK) st = materialize_blocks(ctx, m, BS, &b);
-  if (st == MI_OK) st = mi_lobpcg_gram_pair(ctx, m, k, s, k, a, nullptr, k, b, nullptr, Ga_host, Gb_host);
-  mi_vec_destroy(s);
-  mi_vec_destroy(a);
-  mi_vec_destroy(b);
-  return st;
-}
-
-static bool gram_pair_sym_direct_ok(size_t m, int k, const ColBlocks &S, const mi_vec *Ta1, const mi_vec *Ta2) {
-  return k <= 80 && m % 4 == 0 && (uintptr_t)S.base[0] % 32 == 0 && (uintptr_t)S.base[1] % 32 == 0 &&
-         (uintptr_t)S.base[2] % 32 == 0 && (uintptr_t)Ta1->d % 32 == 0 && (!Ta2 || (uintptr_t)Ta2->d % 32 == 0) && m >= 16;
-}
-
-// S'[Ta1 | Ta2] and S'S, upper block triangles, one pass (k_gram_pair_sym); arguments validated by the callers
-// Tab / Tbb (r05, the generalized problem): T = A(S) and B(S) as column blocks; the second Gram is then S'B(S) instead
-// of S'S, each Gram one launch of k_gram_pair_sym<., false, PAIR = false> (Ta1 / Ta2 unused)
-static int gram_pair_sym_direct(mi_ctx *ctx, size_t m, int k, const ColBlocks &Sb, int k1a, const mi_vec *Ta1,
-                                const mi_vec *Ta2, double *Ga_host, double *Gb_host, const ColBlocks *Tab,
-                                const ColBlocks *Tbb) {
-  const int nelem = k * k, kpad = (k + 15) / 16 * 16;
-  const size_t mfull = m - m % 16;
-  const int occ = kpad <= 32 ? 2 : 1;  // (resident waves per SIMD: 62+16 / 132+48 registers at 1 / 2 tiles, then > 256)
-  const size_t nwaves = (std::min<size_t>(4 * (size_t)occ * ctx->num_cu, mfull / 16) + 3) / 4 * 4;
-  const size_t nb = nwaves;  // (the leftover rows are a step of one of the waves)
-  GramJob jobs[2] = {{nullptr, nullptr, nelem}, {nullptr, nullptr, nelem}};
-  int st = MI_OK;
-  // One rank: the reduction kernel writes the two k x k results STRAIGHT into pinned host memory (82 KB over PCIe at
-  // ns = 72) -- no device buffer, no copy behind the kernel (a blit kernel of ~15 us per Gram even into pinned memory).
-  // Several ranks: the results are all-reduced on the device first.
-  const bool zero_copy = ctx->comm == nullptr && !ctx->cfg.no_zero_copy;
-  const size_t slot = ((size_t)nelem * sizeof(double) + 255) / 256 * 256;
-  char *zc_host = nullptr, *zc_dev = nullptr;
-  if (zero_copy) st = readback_area(ctx, 2 * slot, (void **)&zc_host, (void **)&zc_dev);
-  for (int i = 0; i < 2 && st == MI_OK; ++i) {
-    st = pool_alloc(ctx, nb * (size_t)nelem * sizeof(double), &jobs[i].partial);
-    if (st == MI_OK) {
-      if (zero_copy) jobs[i].Gdev = zc_dev + (size_t)i * slot;
-      else st = pool_alloc(ctx, (size_t)nelem * sizeof(double), &jobs[i].Gdev);
-    }
-  }
-  if (st != MI_OK) {
-    for (int i = 0; i < 2; ++i) {
-      if (jobs[i].partial) pool_free(ctx, jobs[i].partial);
-      if (!zero_copy && jobs[i].Gdev) pool_free(ctx, jobs[i].Gdev);
-    }
-    return st;
-  }
-  if (Tab && Tbb) {  // generalized problem: S'A(S) and S'B(S), one single-Gram launch each
-    KScope ks(ctx, MI_K_LOBPCG_GRAM);
-    for (int i = 0; i < 2; ++i) {
-      const ColBlocks &Tc = i == 0 ? *Tab : *Tbb;
-#define GS1(TT)                                                                                                      \
-  hipLaunchKernelGGL((k_gram_pair_sym<TT, false, false>), dim3((unsigned)(nwaves / 4)), dim3(256), 0, ctx->stream,    \
-                     mfull, m, k, Sb, Tc, (double *)jobs[i].partial, (double *)nullptr)
-      switch (kpad / 16) {
-        case 1: GS1(1); break;
-        case 2: GS1(2); break;
-        case 3: GS1(3); break;
-        case 4: GS1(4); break;
-        default: GS1(5); break;
-      }
-#undef GS1
-    }
-  } else {
-  const double *T2 = Ta2 ? Ta2->d : (Ta1 ? Ta1->d : nullptr);
-  const ColBlocks Tcb = Tab ? *Tab : ColBlocks{{Ta1->d, T2, T2}, k1a, k};  // (Tab alone: T = A(S) as column blocks)
-  // (the last tile column at most half full: it is shared by the two Grams, k_gram_pair_sym<., HALF>)
-  const bool half = k % 16 >= 1 && k % 16 <= 8 && !ctx->cfg.no_gram_half;
-  {
-    KScope ks(ctx, MI_K_LOBPCG_GRAM);
-#define GPS(TT, HF)                                                                                                 \
-  hipLaunchKernelGGL((k_gram_pair_sym<TT, HF, true>), dim3((unsigned)(nwaves / 4)), dim3(256), 0, ctx->stream, mfull, \
-                     m, k, Sb, Tcb, (double *)jobs[0].partial, (double *)jobs[1].partial)
-#define GPSH(TT) \
-  if (half) { GPS(TT, true); } else { GPS(TT, false); }
-    switch (kpad / 16) {
-      case 1: GPSH(1); break;
-      case 2: GPSH(2); break;
-      case 3: GPSH(3); break;
-      case 4: GPSH(4); break;
-      default: GPSH(5); break;
-    }
-#undef GPSH
-#undef GPS
-  }
-  }
-  hipLaunchKernelGGL(k_gram_reduce, dim3((nelem + kRedElems - 1) / kRedElems, 2), dim3(kRedElems * kRedGroups), 0,
-                     ctx->stream, (int)nb, k, nelem, 1, (const double *)jobs[0].partial, (double *)jobs[0].Gdev,
-                     (const double *)jobs[1].partial, (double *)jobs[1].Gdev);
-  if (ctx->comm)
-    for (int i = 0; i < 2; ++i)
-      for (int off = 0; off < nelem && st == MI_OK; off += 4096)
-        st = comm_allreduce(ctx, (double *)jobs[i].Gdev + off, std::min(4096, nelem - off));
-  double *dst[2] = {Ga_host, Gb_host};
-  int fin = MI_OK;
-  if (zero_copy) {
-    fin = stream_wait(ctx, "gram read-back");
-    for (int i = 0; i < 2; ++i) {
-      if (fin == MI_OK) memcpy(dst[i], zc_host + (size_t)i * slot, (size_t)nelem * sizeof(double));
-      pool_free(ctx, jobs[i].partial);
-    }
-  } else {
-    fin = gram_finish(ctx, jobs, 2, dst);
-  }
-  if (st == MI_OK) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) st = hip_fail(e, "symmetric Gram pair launch", __FILE__, __LINE__);
-  }
-  return st != MI_OK ? st : fin;
+  Owned<mi_vec> s, a, b;
+  MI_TRY(materialize_blocks(ctx, m, S, s));
+  MI_TRY(materialize_blocks(ctx, m, AS, a));
+  MI_TRY(materialize_blocks(ctx, m, BS, b));
+  return mi_lobpcg_gram_pair(ctx, m, k, s.get(), k, a.get(), nullptr, k, b.get(), nullptr, Ga_host, Gb_host);
 }
 
 int mi_lobpcg_gram(mi_ctx *ctx, size_t m, int ka, int kb, const mi_vec *S, const mi_vec *T, double *G_host) {
@@ -1787,6 +1674,8 @@ int mi_lobpcg_gram(mi_ctx *ctx, size_t m, int ka, int kb, const mi_vec *S, const
   return gram_impl(ctx, m, ka, kb, S, T, nullptr, kb, G_host);
 }
 
+// the kernel that takes the two pieces as they lie (square panels of <= 80 columns, 32-byte aligned), else
+// T = [T1 | T2] assembled once
 int mi_lobpcg_gram_split(mi_ctx *ctx, size_t m, int k, const mi_vec *S, int k1, const mi_vec *T1, const mi_vec *T2,
                          double *G_host) {
   MI_REQUIRE(ctx && G_host, "null argument");
@@ -1794,21 +1683,10 @@ int mi_lobpcg_gram_split(mi_ctx *ctx, size_t m, int k, const mi_vec *S, int k1, 
   MI_TRY(check_panel(ctx, m, k, S, "S"));
   MI_TRY(check_panel(ctx, m, k1, T1, "T1"));
   MI_TRY(check_panel(ctx, m, k - k1, T2, "T2"));
-  // the kernel that takes the two pieces as they lie (square panels of <= 80 columns, 32-byte aligned) ...
-  const bool direct = k <= 80 && m % 4 == 0 && (uintptr_t)S->d % 32 == 0 && (uintptr_t)T1->d % 32 == 0 &&
-                      (uintptr_t)T2->d % 32 == 0 && m >= 16 * kGdH;
-  if (direct) return gram_impl(ctx, m, k, k, S, T1, T2, k1, G_host);
-  // ... else T = [T1 | T2] assembled once
-  mi_vec *T = nullptr;
-  MI_TRY(mi_vec_create(ctx, m * (size_t)k, &T));
-  hipError_t e = hipMemcpyAsync(T->d, T1->d, m * (size_t)k1 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(T->d + m * (size_t)k1, T2->d, m * (size_t)(k - k1) * sizeof(double), hipMemcpyDeviceToDevice,
-                       ctx->stream);
-  int st = e == hipSuccess ? gram_impl(ctx, m, k, k, S, T, nullptr, k, G_host)
-                           : hip_fail(e, "panel assembly", __FILE__, __LINE__);
-  mi_vec_destroy(T);
-  return st;
+  if (split_direct_ok(m, k, S, T1, T2)) return gram_impl(ctx, m, k, k, S, T1, T2, k1, G_host);
+  Owned<mi_vec> T;
+  MI_TRY(assemble_panel(ctx, m, k, k1, T1, T2, T));
+  return gram_impl(ctx, m, k, k, S, T.get(), nullptr, k, G_host);
 }
 
 int mi_lobpcg_update(mi_ctx *ctx, size_t m, int ks, int kc, const mi_vec *S, const double *C_host, int ldc,
@@ -1858,129 +1736,53 @@ static int update2_impl(mi_ctx *ctx, size_t m, int ks, int kc, const mi_vec *S, 
     }
     if (z0) MI_REQUIRE(z1 <= y0 || z0 >= y1, "the two destination panels overlap");
   }
-  // The matrix-pipe kernel takes the whole-iteration update -- 48 output columns (one chunk) from a basis that cuts into
-  // 6..18 steps of four columns, none straddling two blocks (see StepBases); every other shape goes through the VALU
-  // kernels, which want the basis in one piece.
-  StepBases steps{};
-  struct StepCols { int logical[4]; };  // basis column behind each of the step's four coefficient rows, -1: zero row
-  std::vector<StepCols> step_cols;
-  bool all_mfma = kc > 32 && kc <= 48 && m >= 16 && !ctx->cfg.no_update_mfma;
-  if (all_mfma) {
-    const int nb = blocks ? blocks->nblocks : 1;
-    int start = 0;
-    for (int bi = 0; bi < nb && all_mfma; ++bi) {
-      const int cb = blocks ? blocks->cols[bi] : ks;
-      const double *base = blocks ? blocks->block[bi]->d : S->d;
-      if (cb < 4) all_mfma = false;
-      for (int j = 0; 4 * j < cb && all_mfma; ++j) {
-        const int first = std::min(4 * j, cb - 4);
-        if (step_cols.size() == 18) { all_mfma = false; break; }
-        steps.p[step_cols.size()] = base + (size_t)first * m;
-        StepCols sc;
-        for (int q = 0; q < 4; ++q) sc.logical[q] = first + q >= 4 * j ? start + first + q : -1;
-        step_cols.push_back(sc);
-      }
-      start += cb;
-    }
-    if (step_cols.size() < 6) all_mfma = false;
-    for (size_t i = step_cols.size(); i < 18; ++i) steps.p[i] = steps.p[0];
+  const UpdatePlan plan = update_plan(m, kc, blocks ? blocks->cols : &ks, blocks ? blocks->nblocks : 1,
+                                      ctx->cfg.no_update_mfma);
+  const std::vector<double> Ct = pack_update_coefficients(plan, C_host, ldc);
+  Owned<mi_vec> tmp;
+  if (!S && !plan.all_mfma) {  // (the VALU kernels want the basis in one piece)
+    MI_TRY(materialize_blocks(ctx, m, blocks, tmp));
+    S = tmp.get();
   }
-  // chunk plan (widest chunk that fits what is left: one pass over S per chunk) and the chunks' coefficient blocks,
-  // each ks x KC row-major by s, zero-padded past kc, packed back to back; matrix-pipe form: 4 K4 x 48, one row per
-  // (step, column of the step)
-  struct Chunk { int c0, width; size_t off; };
-  std::vector<Chunk> chunks;
-  size_t total = 0;
-  std::vector<double> Ct;
-  if (all_mfma) {
-    chunks.push_back({0, 48, 0});
-    total = step_cols.size() * 4 * 48;
-    Ct.assign(total, 0.0);
-    for (size_t st_ = 0; st_ < step_cols.size(); ++st_)
-      for (int q = 0; q < 4; ++q) {
-        const int sidx = step_cols[st_].logical[q];
-        if (sidx < 0) continue;
-        for (int c = 0; c < kc; ++c) Ct[(st_ * 4 + q) * 48 + c] = C_host[(size_t)c * ldc + sidx];
-      }
+  PoolBuf Cbuf;
+  MI_TRY(Cbuf.alloc(ctx, plan.total * sizeof(double)));
+  if (plan.total * sizeof(double) <= mi_ctx::kStageBytes) {
+    MI_TRY(stage_upload(ctx, Ct.data(), plan.total * sizeof(double), Cbuf.get()));  // Ct may die: the bytes are in a pinned slot
   } else {
-    for (int c0 = 0; c0 < kc;) {
-      const int left = kc - c0;
-      const int width = left > 32 ? 48 : (left > 16 ? 24 : (left > 8 ? 16 : 8));  // 48 = X and P of one iteration
-      chunks.push_back({c0, width, total});
-      total += (size_t)ks * width;
-      c0 += width;
-    }
-    Ct.assign(total, 0.0);
-    for (const Chunk &ch : chunks)
-      for (int s = 0; s < ks; ++s)
-        for (int c = 0; c < ch.width && ch.c0 + c < kc; ++c)
-          Ct[ch.off + (size_t)s * ch.width + c] = C_host[(size_t)(ch.c0 + c) * ldc + s];
+    hipError_t e = hipMemcpyAsync(Cbuf.get(), Ct.data(), plan.total * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // Ct dies with this call
+    if (e != hipSuccess) return hip_fail(e, "coefficient upload", __FILE__, __LINE__);
   }
-  mi_vec *tmp = nullptr;
-  if (!S && !all_mfma) {
-    MI_TRY(materialize_blocks(ctx, m, blocks, &tmp));
-    S = tmp;
-  }
-  void *Cdev = nullptr;
-  int st = pool_alloc(ctx, total * sizeof(double), &Cdev);
-  if (st == MI_OK) {
-    if (total * sizeof(double) <= mi_ctx::kStageBytes) {
-      st = stage_upload(ctx, Ct.data(), total * sizeof(double), Cdev);  // Ct may die: the bytes are in a pinned slot
-    } else {
-      hipError_t e = hipMemcpyAsync(Cdev, Ct.data(), total * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // Ct dies with this call
-      if (e != hipSuccess) st = hip_fail(e, "coefficient upload", __FILE__, __LINE__);
-    }
-  }
-  if (st != MI_OK) {
-    if (Cdev) pool_free(ctx, Cdev);
-    if (tmp) mi_vec_destroy(tmp);
-    return st;
-  }
-  const int grid = (int)std::min<size_t>((m + 255) / 256, 2048);
+  const double *Cdev = Cbuf.doubles();
+  double *Y2d = Y2 ? Y2->d : nullptr;
   KScope ksc(ctx, MI_K_LOBPCG_UPDATE);
-  for (const Chunk &ch : chunks) {
-#define UPD(KC)                                                                                       \
-  hipLaunchKernelGGL(k_panel_update<KC>, dim3(grid), dim3(256), 0, ctx->stream, m, ks, (const double *)S->d, \
-                     (const double *)Cdev + ch.off, ch.c0, kc, Y->d, k1, Y2 ? Y2->d : (double *)nullptr, r_begin)
-    const size_t r_begin = 0;
-    if (all_mfma) {  // (the m % 16 leftover rows are the last block of one of the waves)
-      // 32-row blocks of two interleaved tiles (16 bytes per lane) when every column start is 16-byte aligned
-      bool pair = m % 2 == 0 && !ctx->cfg.no_update_pair && (uintptr_t)Y->d % 16 == 0 && (!Y2 || (uintptr_t)Y2->d % 16 == 0);
-      for (size_t i = 0; i < 18 && pair; ++i) pair = (uintptr_t)steps.p[i] % 16 == 0;
-      const size_t nblocks = pair ? m / 32 : m / 16;
-      const int mgrid = (int)std::min<size_t>((nblocks + 3) / 4, (size_t)2 * ctx->num_cu);
-#define UPM(K4)                                                                                                \
-  case K4:                                                                                                      \
-    if (pair)                                                                                                   \
-      hipLaunchKernelGGL(k_panel_update_mfma2<K4>, dim3(mgrid), dim3(256), 0, ctx->stream, nblocks, m, steps,    \
-                         (const double *)Cdev + ch.off, kc, Y->d, k1, Y2 ? Y2->d : (double *)nullptr);           \
-    else                                                                                                        \
-      hipLaunchKernelGGL(k_panel_update_mfma<K4>, dim3(mgrid), dim3(256), 0, ctx->stream, nblocks, m, steps,     \
-                         (const double *)Cdev + ch.off, kc, Y->d, k1, Y2 ? Y2->d : (double *)nullptr);           \
-    break
-      switch ((int)step_cols.size()) {
-        UPM(6); UPM(7); UPM(8); UPM(9); UPM(10); UPM(11); UPM(12); UPM(13); UPM(14); UPM(15); UPM(16); UPM(17);
-        default: UPM(18);
-      }
-#undef UPM
-      continue;
+  if (plan.all_mfma) {  // (the m % 16 leftover rows are the last block of one of the waves)
+    StepBases steps{};  // the address of each step's first column; unused entries repeat the first
+    for (int i = 0; i < kPlanMaxSteps; ++i) {
+      const UpdateStep &s = plan.steps[(size_t)i < plan.steps.size() ? i : 0];
+      steps.p[i] = (blocks ? blocks->block[s.block]->d : S->d) + (size_t)s.first * m;
     }
-    switch (ch.width) {
-      case 48: UPD(48); break;
-      case 24: UPD(24); break;
-      case 16: UPD(16); break;
-      default: UPD(8); break;
+    // 32-row blocks of two interleaved tiles (16 bytes per lane) when every column start is 16-byte aligned
+    bool pair = m % 2 == 0 && !ctx->cfg.no_update_pair && aligned_to(16, {(uintptr_t)Y->d, (uintptr_t)Y2d});
+    for (int i = 0; i < kPlanMaxSteps && pair; ++i) pair = (uintptr_t)steps.p[i] % 16 == 0;
+    const size_t nblocks = pair ? m / 32 : m / 16;
+    const int mgrid = (int)std::min<size_t>((nblocks + 3) / 4, (size_t)2 * ctx->num_cu);
+    dispatch_int<6, kPlanMaxSteps>((int)plan.steps.size(), [&](auto k4) {
+      constexpr int K4 = decltype(k4)::value;
+      auto fn = pair ? k_panel_update_mfma2<K4> : k_panel_update_mfma<K4>;
+      hipLaunchKernelGGL(fn, dim3(mgrid), dim3(256), 0, ctx->stream, nblocks, m, steps, Cdev, kc, Y->d, k1, Y2d);
+    });
+  } else {
+    const int grid = (int)std::min<size_t>((m + 255) / 256, 2048);
+    for (const UpdateChunk &ch : plan.chunks) {
+      auto fn = ch.width == 48 ? k_panel_update<48>
+                               : (ch.width == 24 ? k_panel_update<24> : (ch.width == 16 ? k_panel_update<16> : k_panel_update<8>));
+      hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, m, ks, (const double *)S->d, Cdev + ch.off, ch.c0, kc,
+                         Y->d, k1, Y2d, (size_t)0);
     }
-#undef UPD
   }
-  {
-    const hipError_t e = hipGetLastError();
-    st = e == hipSuccess ? MI_OK : hip_fail(e, "panel update launch", __FILE__, __LINE__);
-  }
-  pool_free(ctx, Cdev);  // stream-ordered reuse: later allocations are enqueued after these kernels
-  if (tmp) mi_vec_destroy(tmp);
-  return st;
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MI_OK : hip_fail(e, "panel update launch", __FILE__, __LINE__);
 }
 
 int mi_lobpcg_residual(mi_ctx *ctx, size_t m, int nx, const mi_vec *AX, const mi_vec *BX, const mi_vec *X,
@@ -1992,28 +1794,26 @@ int mi_lobpcg_residual(mi_ctx *ctx, size_t m, int nx, const mi_vec *AX, const mi
   MI_TRY(check_panel(ctx, m, nx, X, "X"));
   touch(R);
   MI_TRY(check_panel(ctx, m, nx, R, "R"));
-  void *thdev = nullptr;
-  MI_TRY(pool_alloc(ctx, (size_t)nx * sizeof(double), &thdev));
-  MI_TRY(stage_upload(ctx, theta_host, (size_t)nx * sizeof(double), thdev));  // (no host wait)
+  PoolBuf thdev, sums;
+  MI_TRY(thdev.alloc(ctx, (size_t)nx * sizeof(double)));
+  MI_TRY(stage_upload(ctx, theta_host, (size_t)nx * sizeof(double), thdev.get()));  // (no host wait)
   const int grid = grid_for(ctx, m, 2);
   // 8 columns per launch (16 reduction components); every chunk's sums land in their own 16 doubles of
   // one device buffer, read back with ONE copy + sync after the last chunk
   const int nchunks = (nx + 7) / 8;
-  void *sums = nullptr;
-  MI_TRY(pool_alloc(ctx, (size_t)nchunks * 16 * sizeof(double), &sums));
+  MI_TRY(sums.alloc(ctx, (size_t)nchunks * 16 * sizeof(double)));
   for (int ch = 0; ch < nchunks; ++ch) {
     {
       KScope ks(ctx, MI_K_LOBPCG_RESIDUAL);
       hipLaunchKernelGGL(k_residual, dim3(grid), dim3(kBlock), 0, ctx->stream, m, nx, 8 * ch, (const double *)AX->d,
-                         (const double *)BX->d, (const double *)X->d, (const double *)thdev, R->d, ctx->partials2);
+                         (const double *)BX->d, (const double *)X->d, (const double *)thdev.doubles(), R->d,
+                         ctx->partials2);
     }
-    MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, grid, 16, (double *)sums + 16 * ch));
+    MI_TRY(reduce_rows_allreduce(ctx, ctx->partials2, grid, 16, sums.doubles() + 16 * ch));
   }
   std::vector<double> out((size_t)nchunks * 16);
-  hipError_t e = hipMemcpyAsync(out.data(), sums, out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e = hipMemcpyAsync(out.data(), sums.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  pool_free(ctx, sums);
-  pool_free(ctx, thdev);
   if (e != hipSuccess) return hip_fail(e, "residual norms read-back", __FILE__, __LINE__);
   for (int c = 0; c < nx; ++c) {
     rnorm[c] = std::sqrt(out[(size_t)(c / 8) * 16 + c % 8]);
@@ -2072,6 +1872,18 @@ bool spmm_win_ok(const mi_csr *A) {
          !csr_row_sharded(A) && A->n * 8 < ((size_t)1 << 32);
 }
 
+// 49 KB of ring at a half-width of two chunks, two workgroups per CU at 212-231 VGPRs (4 columns per pass: 313 us
+// per 24 columns, 8: 251 -> 224-236 with the later changes; r04: 12 columns per pass -- 74 KB of ring, 241-244 VGPRs,
+// still two waves per SIMD -- 234-242 us in the same call: the per-pass costs are not the bound, not kept)
+constexpr int kSpmmWinCols = 8;
+extern "C++" template <int HW, int WC>
+const void *spmm_win_kernel(bool fard, bool res) {
+  if (res) return fard ? (const void *)k_spmm_colmajor_win<kSpmmWinCols, HW, WC, true, true>
+                       : (const void *)k_spmm_colmajor_win<kSpmmWinCols, HW, WC, false, true>;
+  return fard ? (const void *)k_spmm_colmajor_win<kSpmmWinCols, HW, WC, true, false>
+              : (const void *)k_spmm_colmajor_win<kSpmmWinCols, HW, WC, false, false>;
+}
+
 // Y = A X in window form, 8 columns per pass.  theta_host != nullptr: the fused residual form (k_spmm_colmajor_win<..,
 // RES>): R = Y - X diag(theta) and, per pass, the 16 column sums |R_j|^2, |X_j|^2 reduced into sums_dev + 16 * pass.
 bool spmm_sweep_ok(const mi_csr *A);
@@ -2081,23 +1893,12 @@ int spmm_win_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const doub
                     double *sums_dev) {
   mi_ctx *ctx = A->ctx;
   if (spmm_sweep_ok(A)) return spmm_sweep_launch(A, k, Xd, Yd, theta_host, Rd, sums_dev);
-  // 49 KB of ring at a half-width of two chunks, two workgroups per CU at 212-231 VGPRs (4 columns per pass: 313 us
-  // per 24 columns, 8: 251 -> 224-236 with the later changes; r04: 12 columns per pass -- 74 KB of ring, 241-244 VGPRs,
-  // still two waves per SIMD -- 234-242 us in the same call: the per-pass costs are not the bound, not kept)
-  constexpr int kSpmmWinCols = 8;
   const int nc = 2 * kWinWaves + 2 * A->win_chunks;
   const size_t lds = (size_t)kSpmmWinCols * ((size_t)nc * 64 + 1) * sizeof(double);
   const bool hw7 = A->win_head <= 7, wc1 = A->win_chunks == 1, res = theta_host != nullptr;
-  const void *fn = nullptr;
   const bool fard = csr_far_computed(ctx, A);
-#define PICK3(HWV, WCV, FV, RV) fn = (const void *)k_spmm_colmajor_win<kSpmmWinCols, HWV, WCV, FV, RV>
-#define PICK(HWV, WCV)                                                        \
-  if (res) { if (fard) PICK3(HWV, WCV, true, true); else PICK3(HWV, WCV, false, true); } \
-  else { if (fard) PICK3(HWV, WCV, true, false); else PICK3(HWV, WCV, false, false); }
-  if (wc1) { if (hw7) { PICK(7, 1) } else { PICK(8, 1) } }
-  else { if (hw7) { PICK(7, 2) } else { PICK(8, 2) } }
-#undef PICK
-#undef PICK3
+  const void *fn = wc1 ? (hw7 ? spmm_win_kernel<7, 1>(fard, res) : spmm_win_kernel<8, 1>(fard, res))
+                       : (hw7 ? spmm_win_kernel<7, 2>(fard, res) : spmm_win_kernel<8, 2>(fard, res));
   int &occ = ctx->spmm_win_occ[hw7 ? 0 : 1][wc1 ? 0 : 1][fard ? 1 : 0][res ? 1 : 0];
   if (occ == 0) {
     int nbk = 0;
@@ -2118,18 +1919,16 @@ int spmm_win_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const doub
   const int xgrid = (wgrid + kNumXCD - 1) / kNumXCD * kNumXCD;
   if (!res || (ctx->comm == nullptr && xgrid <= kMaxRows)) {
     // all passes in one launch; residual form: the passes' partial rows side by side, one reduction kernel for all
-    void *pr = nullptr;
-    if (res) MI_TRY(pool_alloc(ctx, (size_t)npass * 2 * kSpmmWinCols * kMaxRows * sizeof(double), &pr));
-    double *partials = (double *)pr;
+    PoolBuf pr;
+    if (res) MI_TRY(pr.alloc(ctx, (size_t)npass * 2 * kSpmmWinCols * kMaxRows * sizeof(double)));
+    double *partials = pr.doubles();
     int c0 = 0, nruns = wgrid;
     void *args[] = {&view, &wv, &k, &c0, &nruns, &Xd, &Yd, &theta_arg, &Rd, &partials};
-    hipError_t e = hipLaunchKernel(fn, dim3(xgrid, npass), dim3(kWinBlock), args, lds, ctx->stream);
-    int st = e == hipSuccess ? MI_OK : hip_fail(e, "panel product launch", __FILE__, __LINE__);
-    if (st == MI_OK && res)
-      st = launch_reduce_rows_to_slots(ctx, partials, xgrid, 2 * kSpmmWinCols, sums_dev, npass,
-                                       (size_t)2 * kSpmmWinCols * kMaxRows);
-    if (pr) pool_free(ctx, pr);
-    MI_TRY(st);
+    const hipError_t e = hipLaunchKernel(fn, dim3(xgrid, npass), dim3(kWinBlock), args, lds, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "panel product launch", __FILE__, __LINE__);
+    if (res)
+      MI_TRY(launch_reduce_rows_to_slots(ctx, partials, xgrid, 2 * kSpmmWinCols, sums_dev, npass,
+                                         (size_t)2 * kSpmmWinCols * kMaxRows));
   } else {
     double *partials = ctx->partials2;
     for (int c0 = 0; c0 < k; c0 += kSpmmWinCols) {
@@ -2143,11 +1942,13 @@ int spmm_win_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const doub
   return MI_OK;
 }
 
-// the plane-sweep form applies: packed matrix with a pure far structure, one context, no halo; opt-out NO_SPMM_SWEEP
+// the plane-sweep form applies: packed matrix with a pure far structure whose planes the sweep's grid can hold
+// (lobpcg_plan.h: sweep_fits), one context, no halo; opt-out NO_SPMM_SWEEP
 bool spmm_sweep_ok(const mi_csr *A) {
-  return A->pk && A->win_far_pure >= (size_t)(2 * kSwRows) && A->win_far_pure < ((size_t)1 << 22) && A->win_chunks > 0 &&
-         A->win_chunks <= 2 && A->win_head <= 8 && !A->ctx->cfg.no_spmm_sweep && !A->ctx->uniform_grid &&
-         !csr_row_sharded(A) && A->n < ((size_t)1 << 31) && !A->ctx->comm;
+  return A->pk && A->win_far_pure >= (size_t)(2 * kSwRows) && A->win_far_pure < ((size_t)1 << 22) &&
+         sweep_fits(A->win_far_pure) && A->win_chunks > 0 && A->win_chunks <= 2 && A->win_head <= 8 &&
+         !A->ctx->cfg.no_spmm_sweep && !A->ctx->uniform_grid && !csr_row_sharded(A) && A->n < ((size_t)1 << 31) &&
+         !A->ctx->comm;
 }
 
 int spmm_sweep_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const double *theta_host, double *Rd,
@@ -2159,33 +1960,20 @@ int spmm_sweep_launch(const mi_csr *A, int k, ColBlocks Xd, double *Yd, const do
   const void *fn = nullptr;
   if (res) fn = hw7 ? (const void *)k_spmm_colmajor_sweep<KC, 7, true> : (const void *)k_spmm_colmajor_sweep<KC, 8, true>;
   else fn = hw7 ? (const void *)k_spmm_colmajor_sweep<KC, 7, false> : (const void *)k_spmm_colmajor_sweep<KC, 8, false>;
-  const unsigned D = (unsigned)A->win_far_pure;
-  const int tiles = (int)((D + kSwRows - 1) / kSwRows);
-  const int nst = (int)((A->n + D - 1) / D);
-  const int npass = (k + KC - 1) / KC;
-  // z-segments: enough workgroups to fill the chip twice over in one launch, at most kMaxRows partial rows, and not so
-  // short that a segment's start-up (three plane-tiles loaded for zs computed) weighs more than ~20 %
-  int zsegs = ctx->cfg.sweep_zsegs > 0 ? ctx->cfg.sweep_zsegs : (4 * ctx->num_cu + tiles * npass - 1) / (tiles * npass);
-  zsegs = std::max(1, std::min(zsegs, std::min(nst / 12 > 0 ? nst / 12 : 1, kMaxRows / tiles)));
-  const int zs = (nst + zsegs - 1) / zsegs;
-  zsegs = (nst + zs - 1) / zs;
-  const int xgrid = tiles * zsegs;
-  MI_REQUIRE(xgrid <= kMaxRows, "plane-sweep product: %d workgroups per pass", xgrid);
+  const SweepPlan p = sweep_plan(A->win_far_pure, A->n, k, ctx->num_cu, ctx->cfg.sweep_zsegs);
+  MI_REQUIRE(p.ok && p.xgrid <= kMaxRows, "plane-sweep product: %d workgroups per pass", p.xgrid);
   SellView view = sell_view(A);
   ThetaArg theta_arg{};
   if (res) std::copy(theta_host, theta_host + k, theta_arg.v);
-  void *pr = nullptr;
-  if (res) MI_TRY(pool_alloc(ctx, (size_t)npass * 2 * KC * kMaxRows * sizeof(double), &pr));
-  double *partials = (double *)pr;
-  unsigned Darg = D;
-  int tiles_a = tiles, zs_a = zs, c0 = 0;
-  void *args[] = {&view, &Darg, &tiles_a, &zs_a, &k, &c0, &Xd, &Yd, &theta_arg, &Rd, &partials};
-  hipError_t e = hipLaunchKernel(fn, dim3(xgrid, npass), dim3(kSwBlock), args, lds, ctx->stream);
-  int st = e == hipSuccess ? MI_OK : hip_fail(e, "plane-sweep panel product launch", __FILE__, __LINE__);
-  if (st == MI_OK && res)
-    st = launch_reduce_rows_to_slots(ctx, partials, xgrid, 2 * KC, sums_dev, npass, (size_t)2 * KC * kMaxRows);
-  if (pr) pool_free(ctx, pr);
-  MI_TRY(st);
+  PoolBuf pr;
+  if (res) MI_TRY(pr.alloc(ctx, (size_t)p.npass * 2 * KC * kMaxRows * sizeof(double)));
+  double *partials = pr.doubles();
+  unsigned D = (unsigned)A->win_far_pure;
+  int tiles = p.tiles, zs = p.zs, c0 = 0;
+  void *args[] = {&view, &D, &tiles, &zs, &k, &c0, &Xd, &Yd, &theta_arg, &Rd, &partials};
+  const hipError_t e = hipLaunchKernel(fn, dim3(p.xgrid, p.npass), dim3(kSwBlock), args, lds, ctx->stream);
+  if (e != hipSuccess) return hip_fail(e, "plane-sweep panel product launch", __FILE__, __LINE__);
+  if (res) MI_TRY(launch_reduce_rows_to_slots(ctx, partials, p.xgrid, 2 * KC, sums_dev, p.npass, (size_t)2 * KC * kMaxRows));
   MI_HIP(hipGetLastError());
   return MI_OK;
 }
@@ -2209,35 +1997,32 @@ int mi_csr_spmm_colmajor_residual(const mi_csr *A, int nx, const mi_vec *X, cons
   }
   touch(AX);
   touch(R);
-  const int nchunks = (nx + 7) / 8;
-  void *sums = nullptr;
   // one rank: the 2 nx column sums land straight in pinned host memory (the reduction kernel stores them there), no
   // copy behind the last kernel; several ranks: device buffer + read-back
   const bool zero_copy = ctx->comm == nullptr && !ctx->cfg.no_zero_copy;
-  const size_t nsums = (size_t)nchunks * 16;
-  void *zc_host = nullptr;
-  int st = zero_copy ? readback_area(ctx, nsums * sizeof(double), &zc_host, &sums)
-                     : pool_alloc(ctx, nsums * sizeof(double), &sums);
-  if (st == MI_OK) {
-    KScope ks(ctx, MI_K_SPMM);
-    st = spmm_win_launch(A, nx, ColBlocks{{X->d, X->d, X->d}, nx, nx}, AX->d, theta_host, R->d, (double *)sums);
+  const size_t nsums = (size_t)((nx + 7) / 8) * 16;
+  void *zc_host = nullptr, *sums = nullptr;
+  PoolBuf sums_buf;
+  if (zero_copy) {
+    MI_TRY(readback_area(ctx, nsums * sizeof(double), &zc_host, &sums));
+  } else {
+    MI_TRY(sums_buf.alloc(ctx, nsums * sizeof(double)));
+    sums = sums_buf.get();
   }
-  if (st != MI_OK) {  // (the pool buffer goes back on every path)
-    if (sums && !zero_copy) pool_free(ctx, sums);
-    return st;
+  {
+    KScope ks(ctx, MI_K_SPMM);
+    MI_TRY(spmm_win_launch(A, nx, one_block(X->d, nx), AX->d, theta_host, R->d, (double *)sums));
   }
   std::vector<double> out(nsums);
   if (zero_copy) {
-    st = stream_wait(ctx, "residual norms read-back");
-    if (st == MI_OK) memcpy(out.data(), zc_host, nsums * sizeof(double));
+    MI_TRY(stream_wait(ctx, "residual norms read-back"));
+    memcpy(out.data(), zc_host, nsums * sizeof(double));
   } else {
     const void *dv[1] = {sums};
     const size_t by[1] = {nsums * sizeof(double)};
     void *hs[1] = {out.data()};
-    st = readback_sync(ctx, 1, dv, by, hs);
-    pool_free(ctx, sums);
+    MI_TRY(readback_sync(ctx, 1, dv, by, hs));
   }
-  if (st != MI_OK) return st;
   for (int c = 0; c < nx; ++c) {
     rnorm[c] = std::sqrt(out[(size_t)(c / 8) * 16 + c % 8]);
     xnorm[c] = std::sqrt(out[(size_t)(c / 8) * 16 + 8 + c % 8]);
@@ -2262,11 +2047,9 @@ int mi_csr_spmm_colmajor_blocks(const mi_csr *A, const mi_panel_blocks *X, mi_ve
     KScope ks(ctx, MI_K_SPMM);
     return spmm_win_launch(A, k, cb, Y->d, nullptr, nullptr, nullptr);
   }
-  mi_vec *tmp = nullptr;  // (matrix forms whose product kernels want one panel: the blocks copied together)
-  MI_TRY(materialize_blocks(ctx, A->n, X, &tmp));
-  const int st = mi_csr_spmm_colmajor(A, k, tmp, Y);
-  mi_vec_destroy(tmp);
-  return st;
+  Owned<mi_vec> tmp;  // (matrix forms whose product kernels want one panel: the blocks copied together)
+  MI_TRY(materialize_blocks(ctx, A->n, X, tmp));
+  return mi_csr_spmm_colmajor(A, k, tmp.get(), Y);
 }
 
 int mi_csr_spmm_colmajor(const mi_csr *A, int k, const mi_vec *X, mi_vec *Y) {
@@ -2281,66 +2064,112 @@ int mi_csr_spmm_colmajor(const mi_csr *A, int k, const mi_vec *X, mi_vec *Y) {
     // Row-sharded matrix (8(e): "LOBPCG: row-shard S"): four columns at a time through the row-major sharded
     // product -- its halo exchange is sized for p <= 4 -- at the price of two extra passes over those columns.
     // COLLECTIVE: every rank of the communicator makes the same call.
-    void *vin = nullptr, *vout = nullptr;
-    MI_TRY(pool_alloc(ctx, A->n * 4 * sizeof(double), &vin));
-    int st = pool_alloc(ctx, A->n * 4 * sizeof(double), &vout);
+    PoolBuf vin, vout;
+    MI_TRY(vin.alloc(ctx, A->n * 4 * sizeof(double)));
+    MI_TRY(vout.alloc(ctx, A->n * 4 * sizeof(double)));
     const int tgrid = (int)std::max<size_t>(1, std::min<size_t>((A->n + 255) / 256, 2048));
-    for (int c0 = 0; c0 < k && st == MI_OK; c0 += 4) {
+    for (int c0 = 0; c0 < k; c0 += 4) {
       const int kc = std::min(4, k - c0);
       hipLaunchKernelGGL(k_cols_to_rows, dim3(tgrid), dim3(256), 0, ctx->stream, A->n, kc,
-                         (const double *)X->d + (size_t)c0 * A->n, (double *)vin);
-      st = comm_halo_exchange(ctx, A, kc, (const double *)vin);
-      if (st == MI_OK) st = csr_spmm_launch(A, kc, (const double *)vin, (double *)vout);
-      hipLaunchKernelGGL(k_rows_to_cols, dim3(tgrid), dim3(256), 0, ctx->stream, A->n, kc, (const double *)vout,
+                         (const double *)X->d + (size_t)c0 * A->n, vin.doubles());
+      MI_TRY(comm_halo_exchange(ctx, A, kc, vin.doubles()));
+      MI_TRY(csr_spmm_launch(A, kc, vin.doubles(), vout.doubles()));
+      hipLaunchKernelGGL(k_rows_to_cols, dim3(tgrid), dim3(256), 0, ctx->stream, A->n, kc, (const double *)vout.doubles(),
                          Y->d + (size_t)c0 * A->n);
     }
-    pool_free(ctx, vin);
-    if (vout) pool_free(ctx, vout);
-    MI_TRY(st);
     MI_HIP(hipGetLastError());
     return MI_OK;
   }
   const int grid = (int)((A->nslices + 3) / 4);
   KScope ks(ctx, MI_K_SPMM);
-  if (spmm_win_ok(A)) return spmm_win_launch(A, k, ColBlocks{{X->d, X->d, X->d}, k, k}, Y->d, nullptr, nullptr, nullptr);
-  if (A->pk) {
-    constexpr int chunk = 24;  // (narrower column chunks measured slower: DESIGN 7.5)
-    for (int c0 = 0; c0 < k;) {
-      const int left = k - c0;
-#define SPMMPK(KC)                                                                                            \
-  hipLaunchKernelGGL(k_spmm_colmajor_pk<KC>, dim3(grid), dim3(256), 0, ctx->stream, A->n, A->nslices,         \
-                     (const long long *)A->slice_ptr, (const uint32_t *)A->pk, (const double *)A->vtab, k,    \
-                     c0, (const double *)X->d, Y->d)
-      const int want = std::min(left, chunk);
-      if (want > 16) { SPMMPK(24); c0 += 24; }
-      else if (want > 8) { SPMMPK(16); c0 += 16; }
-      else if (want > 4) { SPMMPK(8); c0 += 8; }
-      else if (want > 2) { SPMMPK(4); c0 += 4; }
-      else { SPMMPK(2); c0 += 2; }
-#undef SPMMPK
-    }
-    MI_HIP(hipGetLastError());
-    return MI_OK;
-  }
+  if (spmm_win_ok(A)) return spmm_win_launch(A, k, one_block(X->d, k), Y->d, nullptr, nullptr, nullptr);
+  // column chunks of at most 24 (narrower ones measured slower: DESIGN 7.5), the narrowest that covers what is left
   for (int c0 = 0; c0 < k;) {
     const int left = k - c0;
-#define SPMM(KC)                                                                                             \
-  hipLaunchKernelGGL(k_spmm_colmajor<KC>, dim3(grid), dim3(256), 0, ctx->stream, A->n, A->nslices,           \
-                     (const long long *)A->slice_ptr, (const int *)A->col, (const double *)A->val, k, c0,    \
-                     (const double *)X->d, Y->d)
-    if (left > 16) {
-      SPMM(24);
-      c0 += 24;
-    } else if (left > 8) {
-      SPMM(16);
-      c0 += 16;
+    if (A->pk) {
+      const int kc = left > 16 ? 24 : (left > 8 ? 16 : (left > 4 ? 8 : (left > 2 ? 4 : 2)));
+      auto fn = kc == 24 ? k_spmm_colmajor_pk<24>
+                         : (kc == 16 ? k_spmm_colmajor_pk<16>
+                                     : (kc == 8 ? k_spmm_colmajor_pk<8> : (kc == 4 ? k_spmm_colmajor_pk<4> : k_spmm_colmajor_pk<2>)));
+      hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, A->n, A->nslices, (const long long *)A->slice_ptr,
+                         (const uint32_t *)A->pk, (const double *)A->vtab, k, c0, (const double *)X->d, Y->d);
+      c0 += kc;
     } else {
-      SPMM(8);
-      c0 += 8;
+      const int kc = left > 16 ? 24 : (left > 8 ? 16 : 8);
+      auto fn = kc == 24 ? k_spmm_colmajor<24> : (kc == 16 ? k_spmm_colmajor<16> : k_spmm_colmajor<8>);
+      hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, A->n, A->nslices, (const long long *)A->slice_ptr,
+                         (const int *)A->col, (const double *)A->val, k, c0, (const double *)X->d, Y->d);
+      c0 += kc;
     }
-#undef SPMM
   }
   MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// ---- host-only: the plans for plain numbers (include/mi355opt.h; tests/test_cpu_lobpcg_plan.py) -----------------------
+int mi_debug_lobpcg_gram_plan(int kind, const size_t *in, size_t *out) {
+  MI_REQUIRE(in && out && kind >= 0 && kind <= 2, "bad argument");
+  if (kind == 2) {  // the eligibility rule and its two minima
+    out[0] = gram_direct_ok(in[0], (int)in[1], in[2] != 0, in[3]);
+    out[1] = kGramDirectMinRows;
+    out[2] = kGramPairMinRows;
+    return MI_OK;
+  }
+  MI_REQUIRE(in[1] >= 1 && in[1] <= (size_t)kGramMaxK, "panel widths must be in [1,%d]", kGramMaxK);
+  if (kind == 1) {
+    MI_REQUIRE(in[4] >= 1 && in[4] < 65536, "bad number of compute units");
+    const GramPairPlan p = gram_pair_plan(in[0], (int)in[1], in[2] != 0, in[3] != 0, (int)in[4]);
+    const size_t v[6] = {(size_t)p.T, p.half, p.pair, (size_t)p.occ, p.nwaves, p.mfull};
+    std::copy(v, v + 6, out);
+    return MI_OK;
+  }
+  MI_REQUIRE(in[2] >= 1 && in[2] <= (size_t)kGramMaxK, "panel widths must be in [1,%d]", kGramMaxK);
+  MI_REQUIRE(in[7] >= 1 && in[7] < 65536, "bad number of compute units");
+  const GramPlan p = gram_plan(in[0], (int)in[1], (int)in[2], in[3] != 0, in[4] != 0, in[5] != 0, in[6] != 0, (int)in[7]);
+  const size_t v[12] = {p.ok, p.direct, p.same, p.aligned, p.tail, (size_t)p.T, (size_t)p.tpw, (size_t)p.occ,
+                        p.nwaves, p.nb, p.mfull, p.lds};
+  std::copy(v, v + 12, out);
+  return MI_OK;
+}
+
+int mi_debug_lobpcg_update_plan(size_t m, int kc, int nblocks, const int *cols, int no_update_mfma, const double *C_host,
+                                int ldc, int *all_mfma, int *nsteps, int *steps, int *nchunks, int *chunks, double *Ct,
+                                size_t ct_cap, size_t *ct_len) {
+  MI_REQUIRE(cols && C_host && all_mfma && nsteps && steps && nchunks && chunks && Ct && ct_len, "null argument");
+  MI_REQUIRE(nblocks >= 1 && nblocks <= 3, "a panel has 1 to 3 column blocks");
+  int ks = 0;
+  for (int i = 0; i < nblocks; ++i) {
+    MI_REQUIRE(cols[i] >= 1, "column block %d is empty", i);
+    ks += cols[i];
+  }
+  MI_REQUIRE(ks <= kGramMaxK && kc >= 1 && kc <= kGramMaxK && ldc >= ks, "bad small-matrix shape");
+  const UpdatePlan p = update_plan(m, kc, cols, nblocks, no_update_mfma != 0);
+  MI_REQUIRE(p.total <= ct_cap && p.chunks.size() <= 4, "the plan needs room for %zu coefficients", p.total);
+  *all_mfma = p.all_mfma;
+  *nsteps = (int)p.steps.size();
+  for (size_t i = 0; i < p.steps.size(); ++i) {
+    const UpdateStep &s = p.steps[i];
+    const int row[6] = {s.block, s.first, s.logical[0], s.logical[1], s.logical[2], s.logical[3]};
+    std::copy(row, row + 6, steps + 6 * i);
+  }
+  *nchunks = (int)p.chunks.size();
+  for (size_t i = 0; i < p.chunks.size(); ++i) {
+    const int row[3] = {p.chunks[i].c0, p.chunks[i].width, (int)p.chunks[i].off};
+    std::copy(row, row + 3, chunks + 3 * i);
+  }
+  const std::vector<double> packed = pack_update_coefficients(p, C_host, ldc);
+  std::copy(packed.begin(), packed.end(), Ct);
+  *ct_len = packed.size();
+  return MI_OK;
+}
+
+int mi_debug_lobpcg_sweep_plan(size_t D, size_t n, int k, int num_cu, int sweep_zsegs, int out[7]) {
+  MI_REQUIRE(out && D >= 1 && D < ((size_t)1 << 31) && n < ((size_t)1 << 31) && k >= 1 && k <= kGramMaxK &&
+                 num_cu >= 1 && num_cu < 65536 && sweep_zsegs >= 0,
+             "bad argument");
+  const SweepPlan p = sweep_plan(D, n, k, num_cu, sweep_zsegs);
+  const int v[7] = {p.ok, p.tiles, p.nst, p.npass, p.zsegs, p.zs, p.xgrid};
+  std::copy(v, v + 7, out);
   return MI_OK;
 }
 

@@ -12,6 +12,7 @@
 #include <memory>
 #include <string>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 #include "mi355opt.h"
@@ -816,6 +817,34 @@ int dev_upload(DevPtr<T> &p, const T *src, size_t count) {
   MI_TRY(upload(&raw, src, count * sizeof(T)));
   p.reset((T *)raw);
   return MI_OK;
+}
+//   PoolBuf          a buffer of the context's pool (pool_free).  Letting it go at scope exit, behind kernels that are
+//                    enqueued but have not run, is sound: pool reuse is stream-ordered, a later allocation's users are
+//                    enqueued after them.  release() hands the buffer to another owner.
+struct PoolFree {
+  mi_ctx *ctx = nullptr;
+  void operator()(void *p) const { pool_free(ctx, p); }
+};
+struct PoolBuf : std::unique_ptr<void, PoolFree> {
+  int alloc(mi_ctx *ctx, size_t bytes) {  // (left as it was on failure)
+    void *raw = nullptr;
+    MI_TRY(pool_alloc(ctx, bytes, &raw));
+    *this = PoolBuf{std::unique_ptr<void, PoolFree>(raw, PoolFree{ctx})};
+    return MI_OK;
+  }
+  double *doubles() const { return (double *)get(); }
+};
+
+// A run-time integer in [Lo, Hi] as a compile-time constant: f(std::integral_constant<int, v>()); values outside the
+// range take the nearest end (the `default:` of the switch ladders this replaces).
+template <int Lo, int Hi, class F>
+void dispatch_int(int v, F &&f) {
+  if constexpr (Lo == Hi) {
+    f(std::integral_constant<int, Lo>());
+  } else {
+    if (v <= Lo) f(std::integral_constant<int, Lo>());
+    else dispatch_int<Lo + 1, Hi>(v, f);
+  }
 }
 
 }  // namespace mi
