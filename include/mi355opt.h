@@ -612,6 +612,47 @@ MI_API int mi_so3n_reweight(mi_so3n *prob, const mi_vec *R, int kind, double c, 
 MI_API int mi_so3n_weights(mi_so3n *prob, double *w_host /* E */);   /* sync: the current w_e */
 
 /* ---------------------------------------------------------------------------------------------
+ * (7b) pose-graph translations: with the rotations R fixed (the 9N point of mi_so3n), the positions of a pose graph with
+ *     edges e = (i -> j), relative translations tt_e (3 per edge) and weights tau_e >= 0 solve the linear least-squares problem
+ *         min_t  f_tau(R, t) = 1/2 sum_e tau_e | t_j - t_i - R_i tt_e |^2    <=>    L_a t = b(R),   t_anchor = 0
+ *     (second stage of chordal initialisation; what SE-Sync does after its rotation solve).  L_a is the tau-weighted graph
+ *     Laplacian with the anchor's row and column -- and the row of every node of weighted degree 0 -- replaced by the unit
+ *     row, acting on the N x 3 row-major field t.  Refused (MI_ERR_INVALID_ARGUMENT, with a message): an anchor or an end
+ *     point outside [0, N), a self-loop, a non-finite tt, a tau that is negative or not finite, a context with a
+ *     communicator (single-context only).  Outside the method and NOT detected: several components that carry edges (CG
+ *     returns a solution of the consistent singular system).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mi_pgo_trans mi_pgo_trans;
+typedef struct mi_pgo_trans_info {
+  size_t iterations;        /* of the PCG solve */
+  int exit_reason;          /* MI_STPCG_EXIT_*: RESIDUAL is convergence; MAXIT, KERNEL and BOUNDARY are reported, not errors */
+  double objective;         /* f_tau(R, t_out) */
+  double relative_residual; /* |L_a t_out - b| / |b| from ONE plain application after the solve, not the recurrence (|b| = 0:
+                               |L_a t_out|) */
+  double max_residual;      /* max_e | t_j - t_i - R_i tt_e | at t_out */
+} mi_pgo_trans_info;
+/* sync (upload).  Owns its mi_csr (L_a), the mi_op of mi_op_create_csr(ctx, L_a, 3) and the mi_precon of
+ * mi_precon_create_diag (1 / diagonal, each value three times). */
+MI_API int mi_pgo_trans_create(mi_ctx *ctx, size_t N, size_t n_edges, const int32_t *ei, const int32_t *ej,
+                               const double *tt /* 3 per edge */, const double *tau, long long anchor, mi_pgo_trans **out);
+MI_API int mi_pgo_trans_destroy(mi_pgo_trans *T);
+/* b (3N) = the right-hand side at R (9N); b_anchor = 0 and b = 0 on nodes of weighted degree 0.  One lane per node, the
+ * incidences summed in slot order, no atomics: the same bits on every run.  No sync. */
+MI_API int mi_pgo_trans_rhs(mi_pgo_trans *T, const mi_vec *R, mi_vec *b);
+/* Borrowed handles (mi_op_destroy / mi_precon_destroy on them are no-ops; they live as long as T), for a caller's own
+ * mi_stpcg: L_a on 3N-vectors with the curvature dots fused, and its Jacobi preconditioner (fused into the CG update).
+ * Either pointer may be null. */
+MI_API int mi_pgo_trans_operator(mi_pgo_trans *T, mi_op **L, mi_precon **jacobi);
+/* r_e = t_j - t_i - R_i tt_e in the caller's edge order into r_out (3E; may be NULL: nothing written, the same out bits);
+ * out = {f_tau(R, t), max_e |r_e|}, both reduced in a fixed order.  One read-back (sync). */
+MI_API int mi_pgo_trans_residual(mi_pgo_trans *T, const mi_vec *R, const mi_vec *t, mi_vec *r_out, double out[2]);
+/* t_out (3N) = the positions: rhs, then mi_stpcg used as plain PCG from t = 0 (g = -b, a radius that never binds, theta = 0,
+ * kappa_fgr = tol: the stop sqrt(<r,v>) <= tol sqrt(<r0,v0>), 0 <= tol < 1), then the residual pass.  t_out[anchor] = 0 and
+ * t_out = 0 on nodes of weighted degree 0, exactly.  Sync. */
+MI_API int mi_pgo_trans_solve(mi_pgo_trans *T, const mi_vec *R, double tol, size_t max_iterations, mi_vec *t_out,
+                              mi_pgo_trans_info *info);
+
+/* ---------------------------------------------------------------------------------------------
  * (8) LOBPCG building blocks (LinearAlgebra/LOBPCG.h:131-337).  Panels are column-major m x k
  *     (ld = m), matching the reference's Eigen dense layout.
  * ------------------------------------------------------------------------------------------- */

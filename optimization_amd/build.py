@@ -149,7 +149,9 @@ def build_harness(force=False):
       tests/cpp/libharness_robust_so3n.so a GNC loop of TNT + MI355::RotationAveraging::reweight, every round repeated on a
                                       fresh problem with the downloaded weights
       tests/cpp/libharness_spectral_so3n.so MI355::RotationAveraging::spectral_initialization, then TNT from the spectral
-                                      point and certify at what it reaches"""
+                                      point and certify at what it reaches
+      tests/cpp/libharness_pgo_trans.so MI355::TranslationRecovery: solve(), and a client's own STPCG call with
+                                      laplacian() and jacobi()"""
     tdir = os.path.join(ROOT, "tests", "cpp")
     inc = ["-I", os.path.join(HERE, "include"), "-I", os.path.join(ROOT, "oracle")]
     common = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-type-limits"]
@@ -194,7 +196,7 @@ def build_harness(force=False):
     # tests/cpp/harness_args.cpp, harness_lsqr_observer.cpp, harness_gd_so3n.cpp, harness_tnls_so3n.cpp: g++, and clang's front end on the same
     # translation units (the pack-carrying instantiations of the template layer must pass both)
     for name in ("harness_args", "harness_lsqr_observer", "harness_gd_so3n", "harness_tnls_so3n", "harness_certify_so3n",
-                 "harness_robust_so3n", "harness_spectral_so3n"):
+                 "harness_robust_so3n", "harness_spectral_so3n", "harness_pgo_trans"):
         src = os.path.join(tdir, name + ".cpp")
         so = os.path.join(tdir, "lib" + name + ".so")
         if force or _newer(src, so, hdrs + [LIB]):
@@ -329,6 +331,8 @@ def build_sanitize(force=False, run=True):
         build_sanitize_so3_pack(force=force, run=run)
     if os.path.exists(os.path.join(tdir, "sanitize_lobpcg_plan.cpp")):
         build_sanitize_lobpcg_plan(force=force, run=run)
+    if os.path.exists(os.path.join(tdir, "sanitize_pgo_trans_pack.cpp")):
+        build_sanitize_pgo_trans_pack(force=force, run=run)
     return exe
 
 
@@ -337,7 +341,7 @@ def _sanitize_header(name, header, force, run):
     tdir = os.path.join(ROOT, "tests", "cpp")
     exe, src = os.path.join(tdir, name), os.path.join(tdir, name + ".cpp")
     asan_opts = _sanitizer_probe(tdir, _SAN)
-    if force or _newer(src, exe, [os.path.join(CSRC, header)]):
+    if force or _newer(src, exe, [os.path.join(CSRC, header), os.path.join(CSRC, "so3_pack.h")]):  # (pgo_trans_pack.h includes it)
         r = subprocess.run(["g++", "-std=c++17", "-Wall"] + _SAN + ["-I", CSRC, src, "-o", exe], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("sanitizer build failed:\n" + r.stderr[-6000:])
@@ -359,6 +363,13 @@ def build_sanitize_lobpcg_plan(force=False, run=True):
     """tests/cpp/sanitize_lobpcg_plan: the plans of the LOBPCG host layer (csrc/lobpcg_plan.h) with the shapes they
     refuse; built and run by build_sanitize() and by tests/test_cpu_lobpcg_plan.py."""
     return _sanitize_header("sanitize_lobpcg_plan", "lobpcg_plan.h", force, run)
+
+
+def build_sanitize_pgo_trans_pack(force=False, run=True):
+    """tests/cpp/sanitize_pgo_trans_pack: the host-side layout of the pose-graph translation solve
+    (csrc/pgo_trans_pack.h, on top of so3_pack.h) with its failure paths; built and run by build_sanitize() and by
+    tests/test_cpu_pgo_trans_pack.py."""
+    return _sanitize_header("sanitize_pgo_trans_pack", "pgo_trans_pack.h", force, run)
 
 
 if __name__ == "__main__":

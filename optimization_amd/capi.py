@@ -91,6 +91,12 @@ class LsqrResult(C.Structure):
 LSQR_EXIT = ["MAXIT", "S1", "S2", "S3", "S4", "TRIVIAL"]
 
 
+class PgoTransInfo(C.Structure):
+    """mi_pgo_trans_info"""
+    _fields_ = [("iterations", C.c_size_t), ("exit_reason", C.c_int), ("objective", C.c_double),
+                ("relative_residual", C.c_double), ("max_residual", C.c_double)]
+
+
 class StpcgTrace(C.Structure):
     _fields_ = [("cap", C.c_size_t), ("len", C.c_size_t), ("alpha", c_double_p), ("beta", c_double_p),
                 ("kappa", c_double_p), ("rv", c_double_p)]
@@ -215,6 +221,13 @@ def load():
         "mi_so3n_project": [vp, vp, vp, c_double_p],
         "mi_so3n_reweight": [vp, vp, C.c_int, C.c_double, c_double_p],
         "mi_so3n_weights": [vp, c_double_p],
+        "mi_pgo_trans_create": [vp, C.c_size_t, C.c_size_t, c_int32_p, c_int32_p, c_double_p, c_double_p, C.c_longlong,
+                                C.POINTER(vp)],
+        "mi_pgo_trans_destroy": [vp],
+        "mi_pgo_trans_rhs": [vp, vp, vp],
+        "mi_pgo_trans_operator": [vp, C.POINTER(vp), C.POINTER(vp)],
+        "mi_pgo_trans_residual": [vp, vp, vp, vp, c_double_p],
+        "mi_pgo_trans_solve": [vp, vp, C.c_double, C.c_size_t, vp, C.POINTER(PgoTransInfo)],
         "mi_stpcg_collect": [vp, C.POINTER(StpcgResult)],
         "mi_lobpcg_gram": [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, c_double_p],
         "mi_lobpcg_update": [vp, C.c_size_t, C.c_int, C.c_int, vp, c_double_p, C.c_int, vp],
@@ -1315,6 +1328,60 @@ class So3N:
         try:
             if self.h and self.ctx.h:
                 self.L.mi_so3n_destroy(self.h)
+        except Exception:  # noqa
+            pass
+
+
+class PgoTranslations:
+    """The translation half of a pose graph (mi_pgo_trans_*): with the rotations R fixed, the positions solve
+    L_a t = b(R) in the gauge t[anchor] = 0."""
+
+    def __init__(self, ctx, N, ei, ej, tt, tau, anchor=0):
+        self.ctx, self.L, self.N = ctx, ctx.L, N
+        ei = np.ascontiguousarray(ei, dtype=np.int32)
+        ej = np.ascontiguousarray(ej, dtype=np.int32)
+        tt = np.ascontiguousarray(tt, dtype=np.float64)
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        assert tt.size == 3 * ei.size and tau.size == ei.size and ej.size == ei.size
+        self.E = ei.size
+        self.h = vp()
+        check(self.L.mi_pgo_trans_create(ctx.h, N, ei.size, ei.ctypes.data_as(c_int32_p), ej.ctypes.data_as(c_int32_p),
+                                         _dp(tt), _dp(tau), int(anchor), C.byref(self.h)))
+
+    def rhs(self, R, out=None):
+        out = out if out is not None else Vec(self.ctx, 3 * self.N)
+        check(self.L.mi_pgo_trans_rhs(self.h, R.h, out.h))
+        return out
+
+    def operator(self):
+        """(L_a as an Op on 3N-vectors, its Jacobi Precon): borrowed, for Context.stpcg"""
+        hop, pc = vp(), vp()
+        check(self.L.mi_pgo_trans_operator(self.h, C.byref(hop), C.byref(pc)))
+        P = Precon.__new__(Precon)
+        P.ctx, P.L, P.h, P.keep = self.ctx, self.L, pc, [self]
+        P.__class__ = _BorrowedPrecon
+        return Op(self.ctx, hop, keep=[self], borrowed=True), P
+
+    def residual(self, R, t, with_vector=True):
+        """(r Vec of 3E or None, f_tau(R, t), max_e |r_e|): one read-back"""
+        r = Vec(self.ctx, 3 * self.E) if with_vector else None
+        out = (C.c_double * 2)()
+        check(self.L.mi_pgo_trans_residual(self.h, R.h, t.h, r.h if with_vector else None, out))
+        return r, out[0], out[1]
+
+    def solve(self, R, tol=1e-10, max_iterations=1000, out=None):
+        """(t Vec, dict(iterations, exit_reason, objective, relative_residual, max_residual))"""
+        t = out if out is not None else Vec(self.ctx, 3 * self.N)
+        info = PgoTransInfo()
+        check(self.L.mi_pgo_trans_solve(self.h, R.h, float(tol), int(max_iterations), t.h, C.byref(info)))
+        return t, dict(iterations=int(info.iterations), exit_reason=STPCG_EXIT[info.exit_reason],
+                       objective=info.objective, relative_residual=info.relative_residual,
+                       max_residual=info.max_residual)
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.L.mi_pgo_trans_destroy(self.h)
         except Exception:  # noqa
             pass
 

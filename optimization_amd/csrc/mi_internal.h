@@ -780,8 +780,8 @@ namespace mi {
 // Owners for the members of a problem object, so that its destructor -- and every early return on the way to a complete
 // one -- releases what was made so far.  Move-only; get(), std::swap and `if (p)` as std::unique_ptr has them.
 //   DevPtr<T>        a hipMalloc allocation of T (hipFree)
-//   Owned<mi_vec>, Owned<mi_op>, Owned<mi_so3n_cert>   a handle (its destroy function; an operator the problem lends out
-//                    as `borrowed` is the owner's to destroy)
+//   Owned<mi_vec>, Owned<mi_op>, Owned<mi_precon>, Owned<mi_csr>, Owned<mi_so3n_cert>   a handle (its destroy function; an
+//                    operator or preconditioner the problem lends out as `borrowed` is the owner's to destroy)
 struct DevFree {
   void operator()(void *p) const { (void)hipFree(p); }
 };
@@ -794,6 +794,11 @@ struct HandleDestroy {
     (void)mi_op_destroy(o);
   }
   void operator()(mi_so3n_cert *c) const;  // so3.hip
+  void operator()(mi_precon *P) const {
+    P->borrowed = false;
+    (void)mi_precon_destroy(P);
+  }
+  void operator()(mi_csr *A) const { (void)mi_csr_destroy(A); }
 };
 template <class T>
 using Owned = std::unique_ptr<T, HandleDestroy>;

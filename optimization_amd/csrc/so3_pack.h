@@ -64,11 +64,16 @@ __attribute__((always_inline)) inline void so3_rotation_to_quat(const double *M,
   qv[0] = w / nrm; qv[1] = x / nrm; qv[2] = y / nrm; qv[3] = z / nrm;
 }
 
-// 0, or 1 with the reason in err (an invalid argument).  no_quat: the measurements stay 3 x 3 matrices (SO3_NO_QUAT);
-// sort_nbr: every node's incidences in ascending order of the NEIGHBOUR instead of edge order (experiment switch
-// SO3_SORT_NBR, "incidences ordered in column phases": measured in DESIGN 5.1; changes the order of a row's sum).
-inline int so3_pack(size_t N, size_t E, const int32_t *ei, const int32_t *ej, const double *Rt, const double *w, bool no_quat,
-                    bool sort_nbr, So3Pack &out, std::string &err) {
+// The graph part of the layout, shared with pgo_trans_pack.h: the SELL-64-sigma slices, the node of every lane, and for
+// every slot its neighbour, its edge (-1: padding) and whether the slot's node is the second (+1) or the first (-1) node.
+struct So3Graph {
+  size_t nslices = 0, nnzb = 0, padded = 0;
+  std::vector<long long> slice_ptr;
+  std::vector<int> perm, nbr, edge;
+  std::vector<signed char> dir;
+};
+// 0, or 1 with the reason in err.  sort_nbr: see so3_pack.
+inline int so3_pack_graph(size_t N, size_t E, const int32_t *ei, const int32_t *ej, bool sort_nbr, So3Graph &out, std::string &err) {
   if (!(N > 0 && N < (size_t)INT32_MAX)) return err = "bad number of rotations", 1;
   for (size_t e = 0; e < E; ++e)
     if (!(ei[e] >= 0 && (size_t)ei[e] < N && ej[e] >= 0 && (size_t)ej[e] < N && ei[e] != ej[e]))
@@ -109,9 +114,11 @@ inline int so3_pack(size_t N, size_t E, const int32_t *ei, const int32_t *ej, co
     sp[s + 1] = sp[s] + (long long)wmax;
   }
   const size_t padded = (size_t)sp[nslices] * 64;
-  std::vector<int> &nbr = out.nbr, edge(padded, -1);
+  std::vector<int> &nbr = out.nbr, &edge = out.edge;
   nbr.assign(padded, 0);
-  std::vector<signed char> dir(padded, 0);
+  edge.assign(padded, -1);
+  std::vector<signed char> &dir = out.dir;
+  dir.assign(padded, 0);
   size_t nnzb = 0;
   for (size_t s = 0; s < nslices; ++s)
     for (int lane = 0; lane < 64; ++lane) {
@@ -130,6 +137,28 @@ inline int so3_pack(size_t N, size_t E, const int32_t *ei, const int32_t *ej, co
         }
       }
     }
+  out.nslices = nslices, out.nnzb = nnzb, out.padded = padded;
+  return 0;
+}
+// the slot words of a graph: edge << 1 | (the slot's node is the first node of the edge); padding 0
+inline void so3_slot_words(const So3Graph &G, std::vector<uint32_t> &words) {
+  words.assign(G.padded, 0u);
+  for (size_t e0 = 0; e0 < G.padded; ++e0)
+    if (G.edge[e0] >= 0) words[e0] = ((uint32_t)G.edge[e0] << 1) | (G.dir[e0] < 0 ? 1u : 0u);
+}
+
+// 0, or 1 with the reason in err (an invalid argument).  no_quat: the measurements stay 3 x 3 matrices (SO3_NO_QUAT);
+// sort_nbr: every node's incidences in ascending order of the NEIGHBOUR instead of edge order (experiment switch
+// SO3_SORT_NBR, "incidences ordered in column phases": measured in DESIGN 5.1; changes the order of a row's sum).
+inline int so3_pack(size_t N, size_t E, const int32_t *ei, const int32_t *ej, const double *Rt, const double *w, bool no_quat,
+                    bool sort_nbr, So3Pack &out, std::string &err) {
+  So3Graph G;
+  if (so3_pack_graph(N, E, ei, ej, sort_nbr, G, err)) return 1;
+  const size_t nslices = G.nslices, padded = G.padded, nnzb = G.nnzb;
+  out.perm = std::move(G.perm), out.slice_ptr = std::move(G.slice_ptr), out.nbr = std::move(G.nbr);
+  const std::vector<long long> &sp = out.slice_ptr;
+  const std::vector<int> &edge = G.edge;
+  const std::vector<signed char> &dir = G.dir;
   // the measurement and weight of every incidence in slot order (k_so3_model streams them), the measurements as unit
   // quaternions when every one of them is a rotation to rounding (k_so3_model<., SQ>)
   const bool all_rot = !no_quat && so3_all_rotations(E, Rt);
@@ -169,9 +198,7 @@ inline int so3_pack(size_t N, size_t E, const int32_t *ei, const int32_t *ej, co
     for (int c = 0; c < scomp; ++c) out.h_Se[(size_t)c * E + e] = qv[c];
   }
   out.h_slot.assign(padded, 0u);
-  if (E < ((size_t)1 << 31))
-    for (size_t e0 = 0; e0 < padded; ++e0)
-      if (edge[e0] >= 0) out.h_slot[e0] = ((uint32_t)edge[e0] << 1) | (dir[e0] < 0 ? 1u : 0u);
+  if (E < ((size_t)1 << 31)) so3_slot_words(G, out.h_slot);
   out.N = N, out.E = E, out.nslices = nslices, out.nnzb = nnzb, out.padded = padded;
   out.sinc_quat = all_rot;
   return 0;
