@@ -113,6 +113,10 @@ enum {
   MI_K_SO3_JACT,        /* k_so3_jact: dF* y over the incidences (apply and apply_sub_scaled forms) */
   MI_K_SO3_EDGE_WEIGHT, /* k_so3_edge_weight: the per-edge pass of mi_so3n_reweight */
   MI_K_SO3_INC_REWEIGHT, /* k_so3_inc_reweight: the per-incidence pass of mi_so3n_reweight */
+  MI_K_PGO_MODEL,       /* k_pgo_model in its model form: the assembly pass of mi_pgo_model */
+  MI_K_PGO_GRAD,        /* k_pgo_model in its other forms: mi_pgo_objective, mi_pgo_gradient, the trial chain */
+  MI_K_PGO_HVP,         /* k_pgo_hvp: the joint Hessian-vector product (with and without the curvature dots) */
+  MI_K_PGO_RETRACT,     /* k_pgo_retract */
   MI_K_COUNT
 };
 /* The library's switches (A/B forms of its kernels, verification hooks of the multi-rank path) are read from the
@@ -653,6 +657,38 @@ MI_API int mi_pgo_trans_solve(mi_pgo_trans *T, const mi_vec *R, double tol, size
                               mi_pgo_trans_info *info);
 
 /* ---------------------------------------------------------------------------------------------
+ * (7c) pose-graph refinement on SE(3)^N: rotations and positions together,
+ *         f(R, t) = 1/2 sum_e kappa_e | R_j - R_i Rt_e |_F^2  +  1/2 sum_e tau_e | t_j - t_i - R_i tt_e |^2,   e = (i -> j).
+ *     Point: 12N doubles [R | t] -- the first 9N in the layout of mi_so3n, the last 3N in the layout of mi_pgo_trans, so a
+ *     mi_vec_view of either half goes to mi_so3n_* / mi_pgo_trans_* and back without a copy.  Tangent: 6N doubles, node-major
+ *     [xi_i (3), delta_i (3)]: the point moves as R_i exp(hat xi_i), t_i + delta_i; the metric is the coordinate dot.  No
+ *     gauge is fixed (the Hessian is semidefinite along the global motions).  kappa is taken as mi_so3n_create takes w.
+ *     Refused (MI_ERR_INVALID_ARGUMENT, with a message): an end point outside [0, N), a self-loop, a non-finite tt, a tau
+ *     that is negative or not finite, a context with a communicator (single-context only).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mi_pgo mi_pgo;
+MI_API int mi_pgo_create(mi_ctx *ctx, size_t N, size_t n_edges, const int32_t *ei, const int32_t *ej,
+                         const double *Rt /* 9 per edge */, const double *tt /* 3 per edge */, const double *kappa,
+                         const double *tau, mi_pgo **out); /* sync (upload) */
+MI_API int mi_pgo_destroy(mi_pgo *prob);
+MI_API int mi_pgo_objective(mi_pgo *prob, const mi_vec *x, double *f); /* sync */
+/* grad f(x) (6N) through the gradient-only form of the assembly pass: the bits of the gradient mi_pgo_model writes; no sync */
+MI_API int mi_pgo_gradient(mi_pgo *prob, const mi_vec *x, mi_vec *grad);
+/* QuadraticModel: the gradient, the Hessian operator assembled at x (one fused pass per product, the curvature dots inside
+ * for mi_stpcg) and the 3x3 block-Jacobi preconditioner of its 2N diagonal blocks (a block without an inverse is replaced
+ * by the identity).  Both handles are borrowed and live as long as prob; either pointer may be null.  No sync. */
+MI_API int mi_pgo_model(mi_pgo *prob, const mi_vec *x, mi_vec *grad, mi_op **hess, mi_precon **block_jacobi);
+/* y = [R_i exp(hat xi_i) | t_i + delta_i]; y must not alias x.  No sync. */
+MI_API int mi_pgo_retract(mi_pgo *prob, const mi_vec *x, const mi_vec *eta, mi_vec *y);
+/* One trial step at the point x the model is bound to (Riemannian/TNT.h:493-512, 573-585): one launch chain, ONE read-back
+ * (sync).  out[6] = {f(x+), <h,h>, <g,h>, <h,Hess h>, |grad f(x+)|^2, |M+^-1 grad f(x+)|^2 with the inverse blocks rebuilt
+ * at x+ (with_precon) or -1}.  Every number has the bits the separate calls (mi_op_apply + mi_vec_dot, mi_pgo_retract,
+ * mi_pgo_objective, mi_pgo_gradient, mi_precon_apply) would produce.  The model stays bound to x: a following
+ * mi_pgo_model(prob, x_trial, ...) assembles afresh. */
+MI_API int mi_pgo_trial(mi_pgo *prob, const mi_vec *x, const mi_vec *h, const mi_vec *g, int with_precon, mi_vec *x_trial,
+                        double out[6]);
+
+/* ---------------------------------------------------------------------------------------------
  * (8) LOBPCG building blocks (LinearAlgebra/LOBPCG.h:131-337).  Panels are column-major m x k
  *     (ld = m), matching the reference's Eigen dense layout.
  * ------------------------------------------------------------------------------------------- */
@@ -788,6 +824,21 @@ MI_API int mi_debug_csr_format_info(const mi_csr *A, size_t out[5]);
 /* read-only: the forms an SO(3)^N problem took -- {measurements stored as unit quaternions, neighbours gathered as
  * quaternions, slices, incidences, padded incidence slots, workgroups of the model assembly}; needs no GPU work */
 MI_API int mi_debug_so3n_info(const mi_so3n *q, size_t out[6]);
+/* Host only (no device needed): the layout csrc/pgo_pack.h builds for a problem of mi_pgo_create, from one run of the
+ * packer.  counts = {N, E, slices, incidences, padded slots}; arrays 0 ... 7 = slice_ptr (long long), perm, nbr (int), the slot
+ * words (uint32_t), rinc, tinc, kinc, tauinc (double): n[a] = the number of elements of array a; up to cap[a] of them are copied
+ * to out[a].  out may be NULL (sizes only). */
+MI_API int mi_debug_pgo_pack(size_t N, size_t n_edges, const int32_t *ei, const int32_t *ej, const double *Rt,
+                             const double *tt, const double *kappa, const double *tau, size_t counts[5], void *const out[8],
+                             const size_t cap[8], size_t n[8]);
+/* The three curvature sums of ONE fused pass of the joint Hessian (the form mi_stpcg drives): h = H eta with the workgroup
+ * partial rows reduced in row order; out = {<eta,h>, <h,h>, <eta,eta>}.  Needs an assembled model.  Sync. */
+MI_API int mi_debug_pgo_hvp_dots(mi_pgo *prob, const mi_vec *eta, mi_vec *h, double out[3]);
+/* What the last mi_pgo_model wrote (sync).  which = 0: kappa B per slot, 1: the coupling blocks per slot (padded * 9 each),
+ * 2: the node blocks in slice order (slices * 19 * 64), 3: the 2N inverse blocks (18N), 4: the inverse blocks the last
+ * mi_pgo_trial with with_precon left at its trial point.  info (nullable) = {slices, incidences, padded slots, workgroups
+ * of the assembly}. */
+MI_API int mi_debug_pgo_blocks(mi_pgo *prob, int which, double *out, size_t cap, size_t *count, size_t info[4]);
 /* Test hook: one application of the operator's fused LSQR form (IterativeSolvers.h:707,712: inout = Op(in) - scale inout
  * with |inout|^2 from the same pass) driven as mi_lsqr drives it; nothing happens when mode != 0.  MI_DECLINED when the
  * operator has no such form.  sync. */

@@ -151,7 +151,9 @@ def build_harness(force=False):
       tests/cpp/libharness_spectral_so3n.so MI355::RotationAveraging::spectral_initialization, then TNT from the spectral
                                       point and certify at what it reaches
       tests/cpp/libharness_pgo_trans.so MI355::TranslationRecovery: solve(), and a client's own STPCG call with
-                                      laplacian() and jacobi()"""
+                                      laplacian() and jacobi()
+      tests/cpp/libharness_pgo.so     TNT on MI355::PoseGraph: tagged accessors, the same callables behind plain lambdas,
+                                      refine(), and the pipeline of examples/pose_graph_refinement.cpp"""
     tdir = os.path.join(ROOT, "tests", "cpp")
     inc = ["-I", os.path.join(HERE, "include"), "-I", os.path.join(ROOT, "oracle")]
     common = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-type-limits"]
@@ -196,7 +198,7 @@ def build_harness(force=False):
     # tests/cpp/harness_args.cpp, harness_lsqr_observer.cpp, harness_gd_so3n.cpp, harness_tnls_so3n.cpp: g++, and clang's front end on the same
     # translation units (the pack-carrying instantiations of the template layer must pass both)
     for name in ("harness_args", "harness_lsqr_observer", "harness_gd_so3n", "harness_tnls_so3n", "harness_certify_so3n",
-                 "harness_robust_so3n", "harness_spectral_so3n", "harness_pgo_trans"):
+                 "harness_robust_so3n", "harness_spectral_so3n", "harness_pgo_trans", "harness_pgo"):
         src = os.path.join(tdir, name + ".cpp")
         so = os.path.join(tdir, "lib" + name + ".so")
         if force or _newer(src, so, hdrs + [LIB]):
@@ -333,6 +335,8 @@ def build_sanitize(force=False, run=True):
         build_sanitize_lobpcg_plan(force=force, run=run)
     if os.path.exists(os.path.join(tdir, "sanitize_pgo_trans_pack.cpp")):
         build_sanitize_pgo_trans_pack(force=force, run=run)
+    if os.path.exists(os.path.join(tdir, "sanitize_pgo_pack.cpp")):
+        build_sanitize_pgo_pack(force=force, run=run)
     return exe
 
 
@@ -370,6 +374,12 @@ def build_sanitize_pgo_trans_pack(force=False, run=True):
     (csrc/pgo_trans_pack.h, on top of so3_pack.h) with its failure paths; built and run by build_sanitize() and by
     tests/test_cpu_pgo_trans_pack.py."""
     return _sanitize_header("sanitize_pgo_trans_pack", "pgo_trans_pack.h", force, run)
+
+
+def build_sanitize_pgo_pack(force=False, run=True):
+    """tests/cpp/sanitize_pgo_pack: the host-side layout of the joint pose-graph problem (csrc/pgo_pack.h, on top of
+    so3_pack.h) with its failure paths; built and run by build_sanitize() and by tests/test_cpu_pgo_pack.py."""
+    return _sanitize_header("sanitize_pgo_pack", "pgo_pack.h", force, run)
 
 
 if __name__ == "__main__":

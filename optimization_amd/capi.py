@@ -19,7 +19,8 @@ KERNELS = ["none", "cg_init", "cg_dot3", "cg_scalar_a", "cg_update", "cg_scalar_
            "csr_spmm", "stiefel_spmm_gram", "stiefel_gram_reduce", "stiefel_finish_dots",
            "stiefel_retract", "bsr3_spmv_dots", "blas1", "lobpcg_gram", "lobpcg_update",
            "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo", "so3_grad",
-           "so3_residual", "so3_jac", "so3_jact", "so3_edge_weight", "so3_inc_reweight"]
+           "so3_residual", "so3_jac", "so3_jact", "so3_edge_weight", "so3_inc_reweight", "pgo_model",
+           "pgo_grad", "pgo_hvp", "pgo_retract"]
 KID = {k: i for i, k in enumerate(KERNELS)}
 STPCG_EXIT = ["RESIDUAL", "MAXIT", "KERNEL", "BOUNDARY", "USER"]
 
@@ -228,6 +229,18 @@ def load():
         "mi_pgo_trans_operator": [vp, C.POINTER(vp), C.POINTER(vp)],
         "mi_pgo_trans_residual": [vp, vp, vp, vp, c_double_p],
         "mi_pgo_trans_solve": [vp, vp, C.c_double, C.c_size_t, vp, C.POINTER(PgoTransInfo)],
+        "mi_pgo_create": [vp, C.c_size_t, C.c_size_t, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                          C.POINTER(vp)],
+        "mi_pgo_destroy": [vp],
+        "mi_pgo_objective": [vp, vp, c_double_p],
+        "mi_pgo_gradient": [vp, vp, vp],
+        "mi_pgo_model": [vp, vp, vp, C.POINTER(vp), C.POINTER(vp)],
+        "mi_pgo_retract": [vp, vp, vp, vp],
+        "mi_pgo_trial": [vp, vp, vp, vp, C.c_int, vp, c_double_p],
+        "mi_debug_pgo_pack": [C.c_size_t, C.c_size_t, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                              c_size_p, C.POINTER(vp), c_size_p, c_size_p],
+        "mi_debug_pgo_hvp_dots": [vp, vp, vp, c_double_p],
+        "mi_debug_pgo_blocks": [vp, C.c_int, c_double_p, C.c_size_t, c_size_p, c_size_p],
         "mi_stpcg_collect": [vp, C.POINTER(StpcgResult)],
         "mi_lobpcg_gram": [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, c_double_p],
         "mi_lobpcg_update": [vp, C.c_size_t, C.c_int, C.c_int, vp, c_double_p, C.c_int, vp],
@@ -1382,6 +1395,113 @@ class PgoTranslations:
         try:
             if self.h and self.ctx.h:
                 self.L.mi_pgo_trans_destroy(self.h)
+        except Exception:  # noqa
+            pass
+
+
+def _pgo_arrays(ei, ej, Rt, tt, kappa, tau):
+    ei = np.ascontiguousarray(ei, dtype=np.int32)
+    ej = np.ascontiguousarray(ej, dtype=np.int32)
+    Rt, tt = np.ascontiguousarray(Rt, dtype=np.float64), np.ascontiguousarray(tt, dtype=np.float64)
+    kappa, tau = np.ascontiguousarray(kappa, dtype=np.float64), np.ascontiguousarray(tau, dtype=np.float64)
+    assert ej.size == ei.size and Rt.size == 9 * ei.size and tt.size == 3 * ei.size and kappa.size == tau.size == ei.size
+    return ei, ej, Rt, tt, kappa, tau
+
+
+PGO_PACK_ARRAYS = (("slice_ptr", np.int64), ("perm", np.int32), ("nbr", np.int32), ("slot", np.uint32), ("rinc", np.float64),
+                   ("tinc", np.float64), ("kinc", np.float64), ("tauinc", np.float64))
+PGO_PACK_COUNTS = ("N", "E", "nslices", "nnzb", "padded")
+
+
+def pgo_pack(N, ei, ej, Rt, tt, kappa, tau):
+    """mi_debug_pgo_pack (host only, no device): the layout of csrc/pgo_pack.h as dict(counts and arrays); a refused
+    problem raises MiError with the packer's reason"""
+    L = load()
+    ei, ej, Rt, tt, kappa, tau = _pgo_arrays(ei, ej, Rt, tt, kappa, tau)
+    args = (int(N), ei.size, ei.ctypes.data_as(c_int32_p), ej.ctypes.data_as(c_int32_p), _dp(Rt), _dp(tt), _dp(kappa), _dp(tau))
+    k = len(PGO_PACK_ARRAYS)
+    counts, n = (C.c_size_t * len(PGO_PACK_COUNTS))(), (C.c_size_t * k)()
+    check(L.mi_debug_pgo_pack(*args, counts, None, None, n))          # the sizes
+    arrays = [np.zeros(n[a], dtype=dtype) for a, (_, dtype) in enumerate(PGO_PACK_ARRAYS)]
+    ptrs = (vp * k)(*[a.ctypes.data_as(vp) for a in arrays])
+    check(L.mi_debug_pgo_pack(*args, counts, ptrs, (C.c_size_t * k)(*[a.size for a in arrays]), n))
+    out = dict(zip(PGO_PACK_COUNTS, (int(c) for c in counts)))
+    out.update({name: a for (name, _), a in zip(PGO_PACK_ARRAYS, arrays)})
+    return out
+
+
+class Pgo:
+    """Joint pose-graph refinement on SE(3)^N (mi_pgo_*): point = 12N doubles [R | t], tangent = 6N doubles [xi_i, delta_i]."""
+
+    def __init__(self, ctx, N, ei, ej, Rt, tt, kappa, tau):
+        self.ctx, self.L, self.N = ctx, ctx.L, N
+        ei, ej, Rt, tt, kappa, tau = _pgo_arrays(ei, ej, Rt, tt, kappa, tau)
+        self.E = ei.size
+        self.h = vp()
+        check(self.L.mi_pgo_create(ctx.h, N, ei.size, ei.ctypes.data_as(c_int32_p), ej.ctypes.data_as(c_int32_p), _dp(Rt),
+                                   _dp(tt), _dp(kappa), _dp(tau), C.byref(self.h)))
+
+    def objective(self, x):
+        f = C.c_double(0)
+        check(self.L.mi_pgo_objective(self.h, x.h, C.byref(f)))
+        return f.value
+
+    def gradient(self, x, out=None):
+        g = out if out is not None else Vec(self.ctx, 6 * self.N)
+        check(self.L.mi_pgo_gradient(self.h, x.h, g.h))
+        return g
+
+    def model(self, x, with_precon=True):
+        """(grad Vec, Hessian Op, block-Jacobi Precon or None), bound to x; the handles are the problem's"""
+        g = Vec(self.ctx, 6 * self.N)
+        hop, pc = vp(), vp()
+        check(self.L.mi_pgo_model(self.h, x.h, g.h, C.byref(hop), C.byref(pc) if with_precon else None))
+        P = None
+        if with_precon:
+            P = Precon.__new__(Precon)
+            P.ctx, P.L, P.h, P.keep = self.ctx, self.L, pc, [self, x]
+            P.__class__ = _BorrowedPrecon
+        return g, Op(self.ctx, hop, keep=[self, x], borrowed=True), P
+
+    def retract(self, x, eta):
+        y = Vec(self.ctx, 12 * self.N)
+        check(self.L.mi_pgo_retract(self.h, x.h, eta.h, y.h))
+        return y
+
+    def trial(self, x, h, g, with_precon=True):
+        """mi_pgo_trial: (x_trial Vec, dict(f, hh, gh, hHh, grad_sqnorm, precon_grad_sqnorm))"""
+        xt = Vec(self.ctx, 12 * self.N)
+        out = np.zeros(6)
+        check(self.L.mi_pgo_trial(self.h, x.h, h.h, g.h, int(with_precon), xt.h, _dp(out)))
+        return xt, dict(f=out[0], hh=out[1], gh=out[2], hHh=out[3], grad_sqnorm=out[4], precon_grad_sqnorm=out[5])
+
+    def hvp_dots(self, eta):
+        """mi_debug_pgo_hvp_dots: (h = H eta Vec, (<eta,h>, <h,h>, <eta,eta>)) from one fused pass of the bound model"""
+        h = Vec(self.ctx, 6 * self.N)
+        out = np.zeros(3)
+        check(self.L.mi_debug_pgo_hvp_dots(self.h, eta.h, h.h, _dp(out)))
+        return h, tuple(out)
+
+    BLOCKS = {"Bblk": 0, "Gblk": 1, "Nsl": 2, "Minv": 3, "Minv_trial": 4}
+
+    def blocks(self, which):
+        """mi_debug_pgo_blocks: one of Pgo.BLOCKS as the last model() (Minv_trial: the last trial()) wrote it"""
+        n = C.c_size_t(0)
+        check(self.L.mi_debug_pgo_blocks(self.h, self.BLOCKS[which], None, 0, C.byref(n), None))
+        a = np.zeros(n.value)
+        check(self.L.mi_debug_pgo_blocks(self.h, self.BLOCKS[which], _dp(a), a.size, C.byref(n), None))
+        return a
+
+    def info(self):
+        """dict(nslices, nnzb, padded, model_grid)"""
+        n, out = C.c_size_t(0), (C.c_size_t * 4)()
+        check(self.L.mi_debug_pgo_blocks(self.h, 0, None, 0, C.byref(n), out))
+        return dict(nslices=int(out[0]), nnzb=int(out[1]), padded=int(out[2]), model_grid=int(out[3]))
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.L.mi_pgo_destroy(self.h)
         except Exception:  # noqa
             pass
 

@@ -368,7 +368,8 @@ static const char *kKernelNames[MI_K_COUNT] = {
     "csr_spmm", "stiefel_spmm_gram", "stiefel_gram_reduce", "stiefel_finish_dots",
     "stiefel_retract", "bsr3_spmv_dots", "blas1", "lobpcg_gram", "lobpcg_update",
     "lobpcg_residual", "stiefel_hess_fused", "comm_allreduce", "comm_halo", "so3_grad",
-    "so3_residual", "so3_jac", "so3_jact", "so3_edge_weight", "so3_inc_reweight"};
+    "so3_residual", "so3_jac", "so3_jact", "so3_edge_weight", "so3_inc_reweight", "pgo_model",
+    "pgo_grad", "pgo_hvp", "pgo_retract"};
 const char *mi_kernel_name(int id) {
   if (id < 0 || id >= MI_K_COUNT) return "?";
   return kKernelNames[id];
