@@ -69,10 +69,19 @@ __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// (hi, lo) += a b with the product and the sum exact (fma residual, two-sum); lo collects the errors unnormalised
+__device__ __forceinline__ void dd_fma(double a, double b, double &hi, double &lo) {
+#pragma clang fp contract(off)
+  const double pr = a * b, pe = __builtin_fma(a, b, -pr);
+  const double s = hi + pr, bb = s - hi, se = (hi - (s - bb)) + (pr - bb);
+  hi = s;
+  lo = lo + (se + pe);
+}
+
 // G^-1/2 of the p x p SPD matrix G (16 doubles a row) by ONE wave: the scaled coupled Newton-Schulz iteration of
 // stiefel.hip dev_sym_invsqrt_wave -- Y0 = G / |G|_F, Z0 = I; T = Z Y; Y <- Y (3 I - T) / 2, Z <- (3 I - T) Z / 2 -- with
-// the same stopping rule, four entries per lane instead of one.  work: 3 * kTallTile doubles of LDS; out: kTallTile,
-// zero outside p x p.
+// the same stopping rule, four entries per lane instead of one, and one corrective step on the unscaled G behind it.
+// work: 3 * kTallTile doubles of LDS; out: kTallTile, zero outside p x p.
 __device__ void tall_invsqrt_wave(const double *G, int p, double *work, double *out) {
   double *T = work, *Y = work + kTallTile, *Z = work + 2 * kTallTile;
   const int l = threadIdx.x & 63;
@@ -136,6 +145,43 @@ __device__ void tall_invsqrt_wave(const double *G, int p, double *work, double *
     const int e = l + 64 * q;
     out[e] = ((e >> 4) < p && (e & 15) < p) ? Z[e] / sqrt(sc) : 0.0;
   }
+  wave_sync_lds();
+  // One corrective step M <- M + M (I - M G M) / 2 on the UNSCALED G.  At cond(G) = 1e6 a float64 M G M carries a
+  // rounding of eps |M| |G| |M| ~ 1e-10, as large as the residual itself, so the two products are accumulated in
+  // double-double (dd_fma); the update is plain.  It halves the loss of orthonormality of Y M that the iteration's own
+  // rounding leaves (tests/test_gpu_stiefel_tall_parity.py, the retractions with cond(Y'Y) up to 1e6).
+  // T, Y <- hi, lo of M G
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = l + 64 * q, i = e >> 4, j = e & 15;
+    double hi = 0, lo = 0;
+    for (int k = 0; k < p; ++k) dd_fma(out[i * 16 + k], G[k * 16 + j], hi, lo);
+    T[e] = hi;
+    Y[e] = lo;
+  }
+  wave_sync_lds();
+  // Z <- I - (M G) M
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = l + 64 * q, i = e >> 4, j = e & 15;
+    double hi = 0, lo = 0;
+    for (int k = 0; k < p; ++k) {
+      dd_fma(T[i * 16 + k], out[k * 16 + j], hi, lo);
+      lo += Y[i * 16 + k] * out[k * 16 + j];
+    }
+    Z[e] = (i < p && j < p) ? ((i == j ? 1.0 : 0.0) - hi) - lo : 0.0;
+  }
+  wave_sync_lds();
+  double c[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = l + 64 * q, i = e >> 4, j = e & 15;
+    c[q] = 0;
+    for (int k = 0; k < p; ++k) c[q] += out[i * 16 + k] * Z[k * 16 + j];
+  }
+  wave_sync_lds();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) out[l + 64 * q] += .5 * c[q];  // (zero outside p x p: M and the residual are)
   wave_sync_lds();
 }
 
